@@ -9,13 +9,24 @@ independent 4096^3 problem: the op has no exchange step when sharded by columns 
 
 Before the W warm-up steps the kernel is launched back to back for >= --prewarm-ms (default 40 ms; reported as prewarm_ms /
 prewarm_launches): the chip needs ~15 ms to clock up from idle, and a caller that asks for five warm-up steps would otherwise
-time the ramp. `roofline.cold20` is the same kernel on an idle chip.
+time the ramp.
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the headline needs: set-up, pre-warm and warm-up, the N
+timed steps, the outputs of the last step if --dump-outputs DIR is given, and the line. Everything else that follows is measured
+only with --full: `roofline.cold20` (the same kernel on an idle chip, before the pre-warm), the per-launch pass, the PMC
+traffic, the MFMA-only ceiling and the secondary sections below.
+
+--dump-outputs DIR writes what the timed path returned in its last step, C = A @ B, as float32: the full C would be 64 MiB,
+so a fixed, seeded sample of its elements is written (DIR/c_sample.npy; DIR/c_sample_rank<r>.npy for rank r > 0). The inputs
+are seeded, so two builds run with the same arguments can be compared output for output.
+
+With --full:
 
 The JSON line is FLAT and small (< 3 KB): besides the contract's fields it carries `config` (workload + every graph / TP /
 all-reduce figure BASELINE.json's metric names as a flat scalar: resnet50_bs128_fp16_graph_ms, bert_base_bs32_seq512_fp16_graph_ms,
 llama7b_block_tp<N>_ms, allreduce_16MiB_{rccl,direct}_busbw_GBs, tp_overlap_{off,on}_ms, gemm4096_{column,k}_shard_*), `roofline`
 (the GEMM + the HBM fractions of Softmax / LayerNorm / the worst memory-bound row) and `cpu_baseline`. The nested detail of the
-sections below is written to gpurun_out/bench_detail_n<N>.json (`--print-detail` also prints it in the line):
+sections below is written to <--detail-dir>/bench_detail_n<N>.json, bench_out/ by default (`--print-detail` also prints it in the line):
   roofline      dominant kernel (the GEMM) vs the dense bf16 MFMA peak, timed with HIP events on
                 the launch stream inside the timed region; `traffic` from the committed PMC passes, only if they were taken
                 from the kernel variant this run launched (config.kernel_variant_launched);
@@ -61,13 +72,20 @@ def parse():
     # (`roofline.cold20`: the first 20 launches on an idle chip).
     ap.add_argument("--prewarm-ms", type=float, default=40.0)
     ap.add_argument("--variant", type=int, default=-1, help="GEMM kernel variant (-1 = heuristic)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline: cold20, per-launch pass, PMC traffic, MFMA ceiling, "
+                         "TP block, graphs, CPU baseline, extras (a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a fixed, seeded float32 sample of the last timed step's output C as DIR/c_sample.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true")
     ap.add_argument("--no-graph", action="store_true", help="skip the ResNet-50 graph-latency row")
     ap.add_argument("--no-tp", action="store_true", help="skip the tensor-parallel block timing")
     ap.add_argument("--print-detail", action="store_true",
                     help="also print the nested sections (tp_block, graph_resnet50, extras) in the line; default: flat scalars in the "
-                         "line, the nested detail in gpurun_out/bench_detail_n<N>.json")
+                         "line, the nested detail in <--detail-dir>/bench_detail_n<N>.json")
+    ap.add_argument("--detail-dir", default=str(REPO / "bench_out"),
+                    help="where --full writes bench_detail_n<N>.json (default: bench_out/ in the repository)")
     ap.add_argument("--secondary-timeout", type=float, default=420.0,
                     help="seconds the secondary sections (TP block, graphs, CPU baseline, extras) may take before the "
                          "headline line is printed without them and the process ends")
@@ -774,6 +792,19 @@ def pmc_traffic(launched: str) -> dict:
 ONE_DEVICE = os.environ.get("IROCM_BENCH_ONE_DEVICE") == "1"
 
 
+def dump_outputs(out_dir: str, c, rank: int, world: int) -> None:
+    """--dump-outputs: the last timed step's C (bf16, M x N) as float32 at (1 << 22) / world fixed flat row-major indices, drawn
+    once from a seeded generator and sorted (16 MiB in all over the ranks; the full C would be 64 MiB per rank)."""
+    import numpy as np
+    import torch
+
+    idx = np.sort(np.random.default_rng(4096).choice(M * N, size=(1 << 22) // world, replace=False))
+    sample = c.reshape(-1)[torch.from_numpy(idx).to(c.device)].float().cpu().numpy()
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    np.save(d / ("c_sample.npy" if rank == 0 else f"c_sample_rank{rank}.npy"), sample)
+
+
 def self_spawn(args) -> int:
     """`python bench.py --gpus N` without a launcher: start N ranks (one process per GPU, RANK / LOCAL_RANK /
     WORLD_SIZE / MASTER_* in the environment — exactly what `python -m torch.distributed.run` would set) and relay
@@ -849,19 +880,21 @@ def main() -> int:
     def step():
         ops.matmul(rt, a, b, out=c)
 
-    # cold figure: 20 launches on an IDLE chip (code objects loaded by two untimed launches, then 0.25 s of nothing: the
-    # clocks are back down)
+    # code objects loaded by two untimed launches
     step()
     step()
     rt.sync()
-    time.sleep(0.25)
-    ec0, ec1 = Event(), Event()
-    rt.record(ec0)
-    for _ in range(20):
-        step()
-    rt.record(ec1)
-    rt.sync()
-    cold_us = rt.elapsed_ms(ec0, ec1) * 1e3 / 20
+    cold_us = None
+    if args.full:
+        # cold figure: 20 launches on an IDLE chip (after the two launches above, 0.25 s of nothing: the clocks are back down)
+        time.sleep(0.25)
+        ec0, ec1 = Event(), Event()
+        rt.record(ec0)
+        for _ in range(20):
+            step()
+        rt.record(ec1)
+        rt.sync()
+        cold_us = rt.elapsed_ms(ec0, ec1) * 1e3 / 20
     kernel_variant_launched = ops.matmul_last_variant(rt)
     # time-based pre-warm (not part of --warmup, stated in the line)
     prewarm_launches = 0
@@ -894,13 +927,15 @@ def main() -> int:
     barrier()
     elapsed = time.perf_counter() - t0
     kernel_s = rt.elapsed_ms(e0, e1) * 1e-3 / args.steps  # avg launch duration from HIP events over the timed region
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, c, rank, world)
     # Per-launch spread, from a SECOND pass of the same launches with an event after every one (<= 1000 steps): it shows
     # the clock state over a run (the chip ramps UP over its first ~150 launches from idle and then holds). Kept out of the
     # timed region: every event record is a marker packet between two dispatches and costs 2-6 us of queue time per launch
     # (measured: 101.6 us per launch with the markers against 95.7 us kernel duration in the rocprofv3 trace of the same run;
     # 96.8 against 94.8 us on another box).
     per_launch = None
-    if args.steps <= 1000:
+    if args.full and args.steps <= 1000:
         marks = [Event() for _ in range(args.steps)]
         m0 = Event()
         rt.record(m0)
@@ -960,17 +995,29 @@ def main() -> int:
             "peak": PEAK_BF16_TFLOPS,
             "unit": "TFLOP/s",
             "frac": round(achieved / PEAK_BF16_TFLOPS, 4),
-            **pmc_traffic(kernel_variant_launched),
             "kernel_us": round(kernel_s * 1e6, 3),
-            # the same kernel on an idle chip: 20 launches after 0.25 s of idleness, before any warm-up
-            "cold20": {"kernel_us": round(cold_us, 3), "achieved": round(flop_per_step / (cold_us * 1e-6) / 1e12, 2),
-                       "frac": round(flop_per_step / (cold_us * 1e-6) / 1e12 / PEAK_BF16_TFLOPS, 4)},
-            "cold20_kernel_us": round(cold_us, 3),
-            "cold20_frac": round(flop_per_step / (cold_us * 1e-6) / 1e12 / PEAK_BF16_TFLOPS, 4),
-            "kernel_us_per_launch": per_launch,
             "peak_from_device": round(info["compute_units"] * 4096 * info["clock_mhz"] * 1e6 / 1e12, 1),
         },
     }
+    if not args.full:
+        if rank == 0:
+            import ctypes
+
+            ctypes.CDLL(None).fflush(None)  # RCCL prints a version banner through C stdio: keep the JSON line last
+            print(json.dumps(line), flush=True)
+        if dist:
+            td.barrier()
+            td.destroy_process_group()
+        return 0
+    line["roofline"].update({
+        **pmc_traffic(kernel_variant_launched),
+        # the same kernel on an idle chip: 20 launches after 0.25 s of idleness, before any warm-up
+        "cold20": {"kernel_us": round(cold_us, 3), "achieved": round(flop_per_step / (cold_us * 1e-6) / 1e12, 2),
+                   "frac": round(flop_per_step / (cold_us * 1e-6) / 1e12 / PEAK_BF16_TFLOPS, 4)},
+        "cold20_kernel_us": round(cold_us, 3),
+        "cold20_frac": round(flop_per_step / (cold_us * 1e-6) / 1e12 / PEAK_BF16_TFLOPS, 4),
+        "kernel_us_per_launch": per_launch,
+    })
     import ctypes
     import threading
 
@@ -980,7 +1027,7 @@ def main() -> int:
     # results as nested objects in front of 9 KB of memory-bound rows, and the second half of BASELINE's metric (ResNet-50 bs128
     # graph ms) never reached BENCH_r04.json. Now: every figure BASELINE.json's metric / north_star names is a flat scalar inside
     # `config` (graph latencies, TP block, all-reduce bus bandwidth) or `roofline` (HBM fractions of Softmax / LayerNorm); the
-    # nested detail of every section goes to a FILE (gpurun_out/bench_detail_n<N>.json, path in the line).
+    # nested detail of every section goes to a FILE (<--detail-dir>/bench_detail_n<N>.json, path in the line).
     detail: dict = {}
 
     def emit(extra: dict | None = None) -> None:
@@ -994,11 +1041,11 @@ def main() -> int:
             except Exception as e:  # noqa: BLE001  (the headline line must go out whatever a secondary section returned)
                 line["summary_error"] = repr(e)[:120]
             try:
-                out_dir = REPO / "gpurun_out"
-                out_dir.mkdir(exist_ok=True)
+                out_dir = Path(args.detail_dir).resolve()
+                out_dir.mkdir(parents=True, exist_ok=True)
                 df = out_dir / f"bench_detail_n{world}.json"
                 df.write_text(json.dumps({"line": line, **detail}, indent=1))
-                line["detail_file"] = str(df.relative_to(REPO))
+                line["detail_file"] = str(df.relative_to(REPO)) if df.is_relative_to(REPO) else str(df)
             except Exception as e:  # noqa: BLE001
                 line["detail_file"] = "not written: " + repr(e)[:80]
             if args.print_detail:

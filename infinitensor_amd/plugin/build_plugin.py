@@ -1,6 +1,6 @@
 """Build the reference graph executor with the Device::ROCM plugin compiled in.
 
-What is built:  infinitensor_amd/plugin/_build/backend.<abi>.so — the reference's own pybind module
+What is built:  oracle/_ref/plugin/backend.<abi>.so — the reference's own pybind module
 `backend` (core + operators + utils + native-CPU kernels + ffi, compiled where they lie under
 /root/reference) PLUS our plugin (infinitensor_amd/plugin/src/*.cc: RocmRuntimeObj and the
 REGISTER_KERNEL'd Device::ROCM kernels), linked against infinitensor_amd/lib/libinfini_rocm.so.
@@ -12,8 +12,9 @@ stored in this repo as patched copies: this script applies them with exact-match
 to temporary copies (a tmp dir that is deleted after the build) and fails if an anchor no longer
 matches. INTEGRATION.md shows the same edits as a diff for a maintainer.
 
-/root/reference does not exist on the GPU box: there the prebuilt .so (git-ignored, shipped by
-gpurun) is used and this script is a no-op.
+The module is compiled from the reference's sources, so it lives next to the reference oracle under
+oracle/_ref/ (never committed) and not inside the package. Where the reference checkout is absent
+the .so that an earlier build() left there is used and this script is a no-op.
 """
 from __future__ import annotations
 
@@ -32,7 +33,7 @@ sys.path.insert(0, str(REPO))
 from tools.cxxbuild import compile_all, link_shared  # noqa: E402
 
 REF = Path("/root/reference")
-OUT = HERE / "_build"
+OUT = REPO / "oracle" / "_ref" / "plugin"
 
 # (reference-relative file, anchor, replacement) — each anchor must match exactly once.
 PATCHES = [
@@ -168,7 +169,7 @@ def build(verbose: bool = True) -> Path | None:
         header_stamp = max(p.stat().st_mtime for p in [HERE / "include/rocm/rocm_runtime.h", Path(__file__), REPO / "include/infini_rocm.h"])
         objs = compile_all(srcs, objdir, flags, stamp=header_stamp)
         ldflags = subprocess.check_output(["python3-config", "--ldflags", "--embed"], text=True).split()
-        link_shared(objs, out, ["-fopenmp", f"-L{lib.parent}", "-linfini_rocm", "-Wl,-rpath,$ORIGIN/../../lib", *ldflags])
+        link_shared(objs, out, ["-fopenmp", f"-L{lib.parent}", "-linfini_rocm", "-Wl,-rpath,$ORIGIN/../../../infinitensor_amd/lib", *ldflags])
     finally:
         shutil.rmtree(overlay, ignore_errors=True)
     return out

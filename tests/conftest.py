@@ -39,7 +39,7 @@ def load_backend_module():
     if "backend" in sys.modules:
         return sys.modules["backend"]
     suffix = sysconfig.get_config_var("EXT_SUFFIX")
-    for p in (REPO / "infinitensor_amd" / "plugin" / "_build" / f"backend{suffix}", REPO / "oracle" / "_ref" / f"backend{suffix}"):
+    for p in (REPO / "oracle" / "_ref" / "plugin" / f"backend{suffix}", REPO / "oracle" / "_ref" / f"backend{suffix}"):
         if p.exists():
             import torch  # noqa: F401  one HIP runtime per process: torch's must be mapped first (see _lib.py)
 
@@ -66,7 +66,7 @@ def plugin_backend():
     """The reference graph executor WITH the Device::ROCM plugin (`backend.RocmRuntime`)."""
     mod = load_backend_module()
     if mod is None or not hasattr(mod, "RocmRuntime"):
-        pytest.skip("plugin build (infinitensor_amd/plugin/_build) not present")
+        pytest.skip("plugin build (oracle/_ref/plugin) not present")
     return mod
 
 

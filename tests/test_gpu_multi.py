@@ -103,7 +103,8 @@ def test_rocm_launch_two_ranks_match_single_gpu(tmp_path):
 def test_bench_spawns_its_own_ranks():
     """`python bench.py --gpus 2` (no launcher): n_gpus 2, a real all-reduce bus bandwidth, TP parity."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "3", "--no-graph", "--print-detail"],
+    r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "3", "--full", "--no-graph",
+                        "--print-detail"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -125,7 +126,7 @@ def test_bench_tp_block_on_one_device_over_the_direct_transport(world):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env.update(IROCM_BENCH_ONE_DEVICE="1", INFINI_ROCM_COMM="direct", HSA_ENABLE_IPC_MODE_LEGACY="0", INFINI_ROCM_DIRECT_TIMEOUT_S="60",
                IROCM_BENCH_TP_DEBUG="1")
-    r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", str(world), "--steps", "5", "--warmup", "2", "--no-graph",
+    r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", str(world), "--steps", "5", "--warmup", "2", "--full", "--no-graph",
                         "--no-cpu-baseline", "--no-extras", "--print-detail"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -10,7 +10,7 @@ def test_plugin_build_is_present_where_reference_exists():
     import sysconfig
     from pathlib import Path
 
-    p = REPO / "infinitensor_amd" / "plugin" / "_build" / f"backend{sysconfig.get_config_var('EXT_SUFFIX')}"
+    p = REPO / "oracle" / "_ref" / "plugin" / f"backend{sysconfig.get_config_var('EXT_SUFFIX')}"
     if Path("/root/reference").exists():
         assert p.exists(), "run __graft_entry__.build()"
 

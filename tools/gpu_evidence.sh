@@ -24,9 +24,9 @@ timeout -k 10 400 bash tools/profile_gemm.sh 8 > $O/prof_gemm.log 2>&1 && cp gpu
 timeout -k 10 400 bash tools/profile_gemm.sh 4 > $O/prof_gemm4.log 2>&1 && cp gpurun_out/prof_gemm/summary.json $O/${R}_gemm256p_pmc.json
 timeout -k 10 300 bash tools/profile_cmd.sh attention_kernel attn_bert -- python tools/attn_cmd.py > $O/prof_attn.log 2>&1 && cp gpurun_out/prof_attn_bert/summary.json $O/${R}_attention_bert_pmc.json
 step "pmc"
-# 3. the bench line (default flags, the driver's flags)
+# 3. the bench line (--full with default flags; the plain run with the driver's flags)
 cd $REPO
-timeout -k 10 700 python bench.py 2> $O/bench.err | clean | grep '^{' | tail -1 > $O/${R}_bench_line.json; cp gpurun_out/bench_detail_n1.json $O/${R}_bench_detail.json 2>/dev/null
+timeout -k 10 700 python bench.py --full --detail-dir $O 2> $O/bench.err | clean | grep '^{' | tail -1 > $O/${R}_bench_line.json; mv $O/bench_detail_n1.json $O/${R}_bench_detail.json 2>/dev/null
 timeout -k 10 400 python bench.py --warmup 5 --steps 20 2>> $O/bench.err | clean | grep '^{' | tail -1 > $O/${R}_bench_line_driverflags.json
 step "bench"
 # 4. graph-level lines and sweeps

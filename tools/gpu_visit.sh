@@ -5,7 +5,7 @@
 #                         parity check + interleaved timing of the bf16 4096^3 headline + the fine K-tile ledger of each
 #         tests:<expr>    python -m pytest tests -m gpu -x -q -k <expr>
 #         testfile:<f>    python -m pytest tests/<f> -m gpu -x -q
-#         bench           python bench.py (default flags) and with the driver's flags
+#         bench           python bench.py --full (default flags) and the plain run with the driver's flags
 #         py:<script+args>  python <script+args> (spaces as written, quote the step)
 REPO=${GRAFT_REPO_ROOT:-/root/repo}
 cd $REPO
@@ -46,7 +46,7 @@ for step in "$@"; do
       timeout 3000 python -m pytest tests/${step#testfile:} -m gpu -x -q 2>&1 | tail -15 | tee -a $O/tests.txt
       ;;
     bench)
-      timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err; cp gpurun_out/bench_detail_n1.json $O/bench_detail.json 2>/dev/null
+      timeout -k 10 600 python bench.py --full --detail-dir $O > $O/bench.json 2> $O/bench.err; mv $O/bench_detail_n1.json $O/bench_detail.json 2>/dev/null
       timeout -k 10 300 python bench.py --warmup 5 --steps 20 > $O/bench_driverflags.json 2>> $O/bench.err
       tail -c 1500 $O/bench_driverflags.json
       ;;

@@ -8,8 +8,9 @@ for m in "resnet50 --batch 128 --iters 3" "bert --batch 32 --seq 512 --iters 3" 
   name=$(echo $m | cut -d' ' -f1)$(echo $m | grep -q decomposed && echo _decomposed)
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$name -o $name -- python $REPO/tools/model_bench.py $m > $OUT/$name.log 2>&1
 done
-# the SAME headline command bench.py runs by default (300 warm-up + 200 timed launches); the secondary sections are switched off
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -o bench -- python $REPO/bench.py --no-cpu-baseline --no-extras --no-graph --no-tp > $OUT/bench.log 2>&1
+# the headline command with --full's cold launches and per-launch pass (300 warm-up + 200 timed launches); the secondary sections are
+# switched off
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -o bench -- python $REPO/bench.py --full --no-cpu-baseline --no-extras --no-graph --no-tp > $OUT/bench.log 2>&1
 python3 - <<PY
 import csv, glob, json
 rows = []
@@ -26,7 +27,7 @@ d = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows]
 # launch order: 300 warm-up, 200 timed, then whatever later sections add (none with the flags above)
 # launch order: 2 + 20 cold launches, the time-based pre-warm (a multiple of 16), 300 warm-up, 200 timed, then the per-launch pass
 timed = d[-400:-200] if len(d) >= 700 else d
-out = {"command": "rocprofv3 --kernel-trace --stats -- python bench.py --no-cpu-baseline --no-extras --no-graph --no-tp",
+out = {"command": "rocprofv3 --kernel-trace --stats -- python bench.py --full --no-cpu-baseline --no-extras --no-graph --no-tp",
        "kernel": rows[0]["Kernel_Name"] if rows else None, "launches": len(d),
        "us_mean_all": sum(d) / max(1, len(d)), "us_mean_timed_200": sum(timed) / max(1, len(timed)),
        "us_min_timed": min(timed) if timed else None, "us_max_timed": max(timed) if timed else None,
