@@ -6,12 +6,14 @@
 // (batch, head) exactly like the reference (attention_kvcache.cu:18).
 // Deviations: the reference exponentiates raw scores (no max subtraction: overflows for |score| > 88)
 // and merges 16-key chunks by their sums — the same value in exact arithmetic; here the usual running-max recurrence.
-// The reference is fp32-only with D == 128; here f32 / f16 / bf16 storage (fp32 math), D a multiple of 128 up to 512.
+// The reference is fp32-only with D == 128; here f32 / f16 / bf16 storage (fp32 math), D in {32, 64, 96, 128, 256}.
 //
 // One workgroup (4 waves) per (batch, head). A 16-lane group owns one key at a time (16 keys in flight per workgroup):
 // each lane holds D/16 consecutive elements of q, dots them with the key row (one coalesced D*sizeof(T) row per group),
 // reduces over the 16 lanes with 4 xor-shuffles, and accumulates its D/16 outputs; the 16 group states are merged
 // through LDS. HBM-bound: 2 * n * D * sizeof(T) bytes per (batch, head).
+// (This element-wise kernel keeps 16 lanes per key at every width — 2, 4 or 6 elements per lane at D = 32, 64, 96; the split
+// kernel below, whose lanes fetch whole 16-byte vectors, puts fewer lanes on a narrow row: kv_lpk.)
 #include "common.h"
 #include <algorithm>
 
@@ -118,6 +120,19 @@ __global__ __launch_bounds__(256) void attention_kvcache_kernel(T *__restrict__ 
 // (batch, head). G = 1 (enough batch x heads to fill the chip by themselves) writes the output directly, one launch.
 // A lane's EPL consecutive elements of one row, fetched as 16-byte vectors and kept PACKED until they are used (the next
 // iteration's rows wait in registers under the current iteration's arithmetic: 4 registers per f16 row piece instead of 8).
+// Lanes per key (LPK) of the split kernel: a row of D elements is D * sizeof(T) / 16 vectors; LPK is the largest power of two that
+// divides that count, at most 16, so that every lane owns the same whole number of vectors (EPL = D / LPK elements):
+//   f16 / bf16: D = 32 -> 4 lanes x 1 vector, 64 -> 8 x 1, 96 -> 4 x 3, 128 -> 16 x 1, 256 -> 16 x 2
+//   f32:        D = 32 -> 8 x 1, 64 -> 16 x 1, 96 -> 8 x 3, 128 -> 16 x 2, 256 -> 16 x 4
+// A 256-thread workgroup therefore holds 256 / LPK key groups and takes 256 / LPK x KPI keys per iteration (the chunk lengths are
+// rounded to that count). infinitensor_amd/ops.py::kvcache_keys_per_iteration states the same rule for the tests of the chunk edges.
+template <typename T> constexpr int kv_lpk(int d) {
+    int vecs = d * (int)sizeof(T) / 16, lpk = 1;
+    while (lpk < 16 && vecs % (2 * lpk) == 0)
+        lpk *= 2;
+    return lpk;
+}
+
 template <typename T, int EPL> struct KvRow;
 template <int EPL> struct KvRow<float, EPL> {
     struct Raw { float4 v[EPL / 4]; };
@@ -179,15 +194,18 @@ template <int EPL> struct KvRow<__hip_bfloat16, EPL> {
 };
 
 // part: [bh][G][D + 2] floats = o[D] (relative to the chunk's own maximum m), m, l
-template <typename T, typename P, int EPL, int KPI, int NG> // KPI = keys per 16-lane group and iteration, NG = 16-lane groups per workgroup
-__global__ __launch_bounds__(NG * 16) void attention_kvcache_split_kernel(T *__restrict__ kc, T *__restrict__ vc, const T *__restrict__ q,
+// EPL = D / LPK elements per lane, KPI = keys per LPK-lane group and iteration, NG = LPK-lane groups per workgroup
+template <typename T, typename P, int EPL, int KPI, int NG, int LPK = 16>
+__global__ __launch_bounds__(NG * LPK) void attention_kvcache_split_kernel(T *__restrict__ kc, T *__restrict__ vc, const T *__restrict__ q,
                                                                       const T *__restrict__ kn, const T *__restrict__ vn,
                                                                       const P *__restrict__ pos, T *__restrict__ out,
                                                                       float *__restrict__ part, int max_seq, int G) {
-    constexpr int D = EPL * 16;
+    static_assert(LPK >= 1 && LPK <= 16 && (LPK & (LPK - 1)) == 0 && EPL * (int)sizeof(T) % 16 == 0, "whole 16-byte vectors per lane");
+    constexpr int D = EPL * LPK;
+    static_assert(D <= NG * LPK, "one thread per output column in the epilogue");
     __shared__ float s_m[NG], s_l[NG], s_o[NG][D];
     const int bh = blockIdx.x, g = blockIdx.y;
-    const int t = threadIdx.x, grp = t >> 4, sub = t & 15;
+    const int t = threadIdx.x, grp = t / LPK, sub = t % LPK;
     const int n = (int)pos[0] + 1; // keys 0 .. n-1; key n-1 is the new one
     if (n < 1 || n > max_seq)
         return;
@@ -239,10 +257,9 @@ __global__ __launch_bounds__(NG * 16) void attention_kvcache_split_kernel(T *__r
 #pragma unroll
             for (int e = 0; e < EPL; ++e)
                 dot = fmaf(qv[e], kf[e], dot);
-            dot += __shfl_xor(dot, 1);
-            dot += __shfl_xor(dot, 2);
-            dot += __shfl_xor(dot, 4);
-            dot += __shfl_xor(dot, 8);
+#pragma unroll
+            for (int x = 1; x < LPK; x <<= 1) // log2(LPK) steps, inside the key's own lanes
+                dot += __shfl_xor(dot, x);
             sc[i] = base + i < c1 ? dot : -INFINITY;
         }
         float m_new = m;
@@ -279,18 +296,33 @@ __global__ __launch_bounds__(NG * 16) void attention_kvcache_split_kernel(T *__r
     for (int e = 0; e < EPL; ++e)
         s_o[grp][e0 + e] = o[e];
     __syncthreads();
-    if (t < D) {
-        float mm = -INFINITY;
+    float mm = -INFINITY, ll = 0.f, oo = 0.f;
 #pragma unroll
-        for (int gg = 0; gg < NG; ++gg)
-            mm = fmaxf(mm, s_m[gg]);
-        float ll = 0.f, oo = 0.f;
+    for (int gg = 0; gg < NG; ++gg)
+        mm = fmaxf(mm, s_m[gg]);
+    if constexpr (NG > 16) {
+        // 32 or 64 key groups (narrow heads): thread gg turns the maximum of group gg into its weight ONCE, in place. (With 16 groups
+        // every column thread recomputes the 16 weights, which is cheaper than two more barriers.)
+        __syncthreads(); // every thread holds mm: s_m may be overwritten
+        if (t < NG)
+            s_m[t] = s_m[t] == -INFINITY ? 0.f : expf(s_m[t] - mm);
+        __syncthreads();
+        if (t < D) {
+#pragma unroll 16
+            for (int gg = 0; gg < NG; ++gg) {
+                ll += s_l[gg] * s_m[gg];
+                oo += s_o[gg][t] * s_m[gg];
+            }
+        }
+    } else if (t < D) {
 #pragma unroll
         for (int gg = 0; gg < NG; ++gg) {
             const float wgt = s_m[gg] == -INFINITY ? 0.f : expf(s_m[gg] - mm);
             ll += s_l[gg] * wgt;
             oo += s_o[gg][t] * wgt;
         }
+    }
+    if (t < D) {
         if (G == 1) {
             KvLd<T>::st(out + (long)bh * D + t, oo / ll);
         } else {
@@ -307,8 +339,10 @@ __global__ __launch_bounds__(NG * 16) void attention_kvcache_split_kernel(T *__r
 // G <= 64: wave 0 reads the G (m, l) pairs in ONE round trip (lane g), reduces them with shuffles and leaves the G weights in LDS;
 // every thread then sums its column over the chunks with the loads of eight chunks in flight. (The first version walked the chunks
 // in two dependent loops: two memory round trips per chunk, 5.4 us for G = 8 — a quarter of the whole decode step.)
+// A whole first wave does that reduction, so the kernel is launched with max(D, 64) threads: D = 32 leaves the upper half of its one
+// wave without a column (a shuffle must not read a lane that was never launched), D = 96 is one and a half waves.
 template <typename T, typename P, int D>
-__global__ __launch_bounds__(D) void attention_kvcache_merge_kernel(const float *__restrict__ part, const P *__restrict__ pos, T *__restrict__ out,
+__global__ __launch_bounds__(D < 64 ? 64 : D) void attention_kvcache_merge_kernel(const float *__restrict__ part, const P *__restrict__ pos, T *__restrict__ out,
                                                                       int max_seq, int G) {
     __shared__ float s_w[64], s_l;
     const int bh = blockIdx.x, t = threadIdx.x;
@@ -333,6 +367,10 @@ __global__ __launch_bounds__(D) void attention_kvcache_merge_kernel(const float 
             s_l = ll;
     }
     __syncthreads();
+    if constexpr (D < 64) {
+        if (t >= D)
+            return;
+    }
     float oo = 0.f;
     int g = 0;
     for (; g + 8 <= G; g += 8) {
@@ -360,8 +398,8 @@ extern "C" int infini_rocm_attention_kvcache(infiniRocmRuntime_t rt, int dtype, 
     IROCM_CHECK_ARG(rt, "NULL runtime");
     IROCM_CHECK_ARG(batch_heads >= 0 && max_seq > 0 && batch_heads < (1ll << 31) && max_seq < (1ll << 31),
                     "attention_kvcache: bad extent");
-    IROCM_CHECK_ARG(head_dim == 128 || head_dim == 256, "attention_kvcache: head dim %lld not in {128, 256} (reference: 128 only)",
-                    (long long)head_dim);
+    IROCM_CHECK_ARG(head_dim == 32 || head_dim == 64 || head_dim == 96 || head_dim == 128 || head_dim == 256,
+                    "attention_kvcache: head dim %lld not in {32, 64, 96, 128, 256} (reference: 128 only)", (long long)head_dim);
     if (batch_heads == 0)
         return INFINI_ROCM_OK;
     IROCM_CHECK_ARG(k_cache && v_cache && q && k && v && position_id && out, "attention_kvcache: NULL tensor");
@@ -388,18 +426,25 @@ extern "C" int infini_rocm_attention_kvcache(infiniRocmRuntime_t rt, int dtype, 
             return st;
         part = (float *)ws;
     }
+    // E = D / 16 names the width; L = kv_lpk lanes per key of the split kernel. D = 128 / 256 give L = 16 and the template arguments
+    // <E, 4, 16> (LPK at its default) they have always had; narrower heads give 256 / L key groups of L lanes, E * 16 / L elements each.
 #define GO(T, P, E)                                                                                        \
-    if (vec_ok && G >= 1) {                                                                                \
-        hipLaunchKernelGGL((attention_kvcache_split_kernel<T, P, E, 4, 16>), dim3((unsigned)batch_heads, (unsigned)G), dim3(256), 0, \
+    do {                                                                                                   \
+        constexpr int L = kv_lpk<T>((E) * 16);                                                             \
+        if (vec_ok && G >= 1) {                                                                            \
+            hipLaunchKernelGGL((attention_kvcache_split_kernel<T, P, (E) * 16 / L, 4, 256 / L, L>),        \
+                               dim3((unsigned)batch_heads, (unsigned)G), dim3(256), 0,                     \
                                rt->stream, (T *)k_cache, (T *)v_cache, (const T *)q, (const T *)k, (const T *)v, \
                                (const P *)position_id, (T *)out, part, (int)max_seq, G);                   \
-        if (G > 1)                                                                                         \
-            hipLaunchKernelGGL((attention_kvcache_merge_kernel<T, P, E * 16>), dim3((unsigned)batch_heads), dim3(E * 16), 0, \
-                               rt->stream, part, (const P *)position_id, (T *)out, (int)max_seq, G);        \
-    } else                                                                                                 \
-        hipLaunchKernelGGL((attention_kvcache_kernel<T, P, E>), dim3((unsigned)batch_heads), dim3(256), 0,  \
-                           rt->stream, (T *)k_cache, (T *)v_cache, (const T *)q, (const T *)k, (const T *)v, \
-                           (const P *)position_id, (T *)out, (int)max_seq)
+            if (G > 1)                                                                                     \
+                hipLaunchKernelGGL((attention_kvcache_merge_kernel<T, P, (E) * 16>), dim3((unsigned)batch_heads), \
+                                   dim3((E) * 16 < 64 ? 64 : (E) * 16), 0,                                 \
+                                   rt->stream, part, (const P *)position_id, (T *)out, (int)max_seq, G);    \
+        } else                                                                                             \
+            hipLaunchKernelGGL((attention_kvcache_kernel<T, P, E>), dim3((unsigned)batch_heads), dim3(256), 0, \
+                               rt->stream, (T *)k_cache, (T *)v_cache, (const T *)q, (const T *)k, (const T *)v, \
+                               (const P *)position_id, (T *)out, (int)max_seq);                            \
+    } while (0)
 #define GOP(T, E)                                                                                          \
     switch (pos_dtype) {                                                                                   \
     case INFINI_DT_I32: GO(T, int32_t, E); break;                                                          \
@@ -408,7 +453,13 @@ extern "C" int infini_rocm_attention_kvcache(infiniRocmRuntime_t rt, int dtype, 
     default: IROCM_FAIL(INFINI_ROCM_UNSUPPORTED, "attention_kvcache: position_id must be int32/uint32/int64"); \
     }
 #define GOD(T)                                                                                             \
-    if (head_dim == 128) { GOP(T, 8) } else { GOP(T, 16) }
+    switch (head_dim) {                                                                                    \
+    case 32: GOP(T, 2) break;                                                                              \
+    case 64: GOP(T, 4) break;                                                                              \
+    case 96: GOP(T, 6) break;                                                                              \
+    case 128: GOP(T, 8) break;                                                                             \
+    default: GOP(T, 16) break;                                                                             \
+    }
     switch (dtype) {
     case INFINI_DT_F32: GOD(float); break;
     case INFINI_DT_F16: GOD(__half); break;

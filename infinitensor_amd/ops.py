@@ -311,10 +311,32 @@ def attention(rt: RocmRuntime, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor
     return out
 
 
+KVCACHE_HEAD_DIMS = (32, 64, 96, 128, 256)
+
+
+def kvcache_lanes_per_key(dtype: torch.dtype, head_dim: int) -> int:
+    """Lanes that share one key row in the split decode kernel (csrc/attention_kvcache.hip::kv_lpk, the same rule): the
+    largest power of two, at most 16, that divides the row's count of 16-byte vectors."""
+    if head_dim not in KVCACHE_HEAD_DIMS:
+        raise ValueError(f"head dim {head_dim} not in {KVCACHE_HEAD_DIMS}")
+    vecs = head_dim * torch.empty(0, dtype=dtype).element_size() // 16
+    lpk = 1
+    while lpk < 16 and vecs % (2 * lpk) == 0:
+        lpk *= 2
+    return lpk
+
+
+def kvcache_keys_per_iteration(dtype: torch.dtype, head_dim: int) -> int:
+    """Keys one workgroup of the split decode kernel takes per loop iteration (256 threads / lanes per key x 4 keys per
+    group); chunk lengths are rounded up to a multiple of it."""
+    return 256 // kvcache_lanes_per_key(dtype, head_dim) * 4
+
+
 def attention_kvcache(rt: RocmRuntime, k_cache: torch.Tensor, v_cache: torch.Tensor, q: torch.Tensor, k: torch.Tensor,
                       v: torch.Tensor, position_id: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
     """Decode step (operators/attention_kvcache.h): caches [B, H, max_seq, D] are appended IN PLACE at
-    position_id[0]; q, k, v [B, H, 1, D]; returns [B, H, 1, D]."""
+    position_id[0]; q, k, v [B, H, 1, D]; returns [B, H, 1, D]. f32 / f16 / bf16, D in KVCACHE_HEAD_DIMS (any other width
+    raises); position_id int32 / uint32 / int64 on the device."""
     if k_cache.dim() != 4 or k_cache.shape != v_cache.shape:
         raise ValueError("caches must be rank-4 [B, H, max_seq, D]")  # reference: IT_ASSERT(rank == 4)
     b, h, ms, d = k_cache.shape

@@ -286,6 +286,8 @@ class RMSNormRocm : public RocmKernelWithoutConfig {
 };
 REGISTER_KERNEL(Device::ROCM, OpType::RMSNorm, RMSNormRocm, "RMSNorm_ROCM");
 
+// One decode step. Head dim D in {32, 64, 96, 128, 256} (the reference kernel: 128 only), f32 / f16 / bf16; any other width is the
+// library's INVALID_ARGUMENT, raised by ROCM_CALL. The caches are appended in place, so consecutive runs of one graph decode on.
 class AttentionKVCacheRocm : public RocmKernelWithoutConfig {
     void compute(const Operator &_op, const RuntimeObj *ctx) const override {
         auto op = as<AttentionKVCacheObj>(_op);

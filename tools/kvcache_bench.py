@@ -1,5 +1,6 @@
 """Decode attention (AttentionKVCache) timing: B x H heads, n cached keys, head dim D; bytes = 2 n D sizeof(T) per head.
-  python tools/kvcache_bench.py [--bh 32 --n 4096 --d 128 --dtype f16] [--splits 0,1,-1]   (-1 = the heuristic)"""
+  python tools/kvcache_bench.py [--bh 32 --n 4096 --head-dim 128 --dtype f16] [--splits 0,1,-1]   (-1 = the heuristic)
+--head-dim (or --d): 32, 64, 96, 128 or 256; the line also names the lanes per key (LPK) of the split kernel at that width."""
 import argparse
 import os
 import sys
@@ -14,7 +15,7 @@ from infinitensor_amd.runtime import Event  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--bh", type=int, default=32)
 ap.add_argument("--n", type=int, default=4096)
-ap.add_argument("--d", type=int, default=128)
+ap.add_argument("--head-dim", "--d", dest="d", type=int, default=128, choices=ops.KVCACHE_HEAD_DIMS)
 ap.add_argument("--dtype", default="f16")
 ap.add_argument("--splits", default="0,1,-1")
 a = ap.parse_args()
@@ -50,4 +51,4 @@ for sp in (int(x) for x in a.splits.split(",")):
     rt.record(e1)
     rt.sync()
     us = rt.elapsed_ms(e0, e1) / iters * 1e3
-    print(f"bh {a.bh} n {a.n} d {a.d} {a.dtype} split {sp:>2}: {us:8.1f} us  {nbytes / us / 1e3:8.1f} GB/s  {nbytes / us / 1e3 / 8000:.3f} of 8 TB/s ({sets} rotating cache sets)")
+    print(f"bh {a.bh} n {a.n} d {a.d} lpk {ops.kvcache_lanes_per_key(dt, a.d)} {a.dtype} split {sp:>2}: {us:8.1f} us  {nbytes / us / 1e3:8.1f} GB/s  {nbytes / us / 1e3 / 8000:.3f} of 8 TB/s ({sets} rotating cache sets)")
