@@ -446,6 +446,15 @@ int infini_rocm_conv2d_set_variant(infiniRocmRuntime_t rt, int variant);
  * workgroups), "tap_shifted" (the other kernels of conv_s1.hip), "batched_gemm", "generic", "none". A forced
  * variant falls back when a shape does not qualify; tests and measurement tools read the route instead of assuming it. */
 int infini_rocm_conv2d_last_route(infiniRocmRuntime_t rt, const char **route);
+/* What the next conv2d call with this problem would launch first, without a runtime or a GPU: the route name (as conv2d_last_route
+ * reports it) and, for "tap_shifted" / "resident", the kernel form of csrc/conv_s1.hip ("pw", "rowtap", "patch_wide", "patch", "resident",
+ * "s1<1,4,32>", "s1<2,2,32>", "s1<2,2,64>"; "" otherwise). Shape rules as conv2d (reference: src/operators/conv.cc:47-114, output extent
+ * conv.cc:98-101); `variant` as conv2d_set_variant, `num_cu` the device's compute units. The planner (csrc/conv_route.h) assumes that the
+ * tensors qualify: a call whose pointers are misaligned, exceed 32-bit offsets or sit at the edge of their allocation takes the next
+ * candidate. Both strings are static. Pure. */
+int infini_rocm_conv2d_plan_route(int dtype, int64_t n, int64_t c, int64_t h, int64_t wd, int64_t f, int64_t r, int64_t s, int ph, int pw,
+                                  int sh, int sw, int dh, int dw, int64_t groups, int act, int has_residual, int variant, int num_cu,
+                                  const char **route, const char **form);
 /* The stem of a CNN as one launch (csrc/conv_stem.hip): y = MaxPool(pool_k x pool_k, stride pool_s, pad pool_p)(act(conv2d(x, w) +
  * bias)) — the chain Conv -> Reshape(bias) -> Add -> Relu -> MaxPool the front-end emits for ResNet's first layers (reference:
  * conv.cc:57-168, element_wise.cu, unary.cc:70-122, pooling.cc:6-95 as four kernels). The conv tile is pooled out of LDS: the conv

@@ -22,6 +22,7 @@
 //   infini_rocm_matmul's LDS-DMA kernels by the dispatcher when the plane size allows 16-byte rows.
 // conv_direct32 (f32): one output per thread, serial fp32 fma over k in the oracle's order.
 #include "gemm_common.h"
+#include "conv_internal.h"
 #include <type_traits>
 
 extern "C" int infini_rocm_matmul(infiniRocmRuntime_t rt, int dtype, const void *a, const void *b,
@@ -45,17 +46,6 @@ template <> struct CvtT<__hip_bfloat16> {
     __device__ static inline float ld(const __hip_bfloat16 *p) { return __bfloat162float(*p); }
     __device__ static inline void st(__hip_bfloat16 *p, float v) { *p = __float2bfloat16(v); }
 };
-
-int launch_conv_s1(infiniRocmRuntime_t rt, int dtype, const void *x, const void *w, const void *bias, const void *res,
-                   void *y, int n, int c, int h, int wd, int f, int r, int s, int ph, int pw, int sh, int sw, int dh, int dw,
-                   int oh, int ow, int act); // conv_s1.hip
-
-int launch_conv_depthwise(infiniRocmRuntime_t rt, int dtype, const void *x, const void *w, const void *bias, void *y, int64_t n, int64_t c,
-                          int64_t h, int64_t wd, int64_t f, int r, int s, int ph, int pw, int sh, int sw, int oh, int ow, int act); // conv_dw.hip
-
-int launch_conv_igemm32(infiniRocmRuntime_t rt, const void *x, const void *w, const void *bias, const void *res, void *y, int64_t n,
-                        int64_t c, int64_t h, int64_t wd, int64_t f, int r, int s, int ph, int pw, int sh, int sw, int dh, int dw, int oh,
-                        int ow, int act); // gemm32.hip
 
 struct ConvArgs {
     const void *x, *w, *bias, *res; // res: optional residual of y's shape, added before the activation
@@ -404,11 +394,30 @@ __global__ __launch_bounds__(256) void conv_transpose_direct(const T *__restrict
 
 using namespace irocm;
 
-namespace irocm {
-// gemm256p_conv.hip: a unit-stride pointwise convolution as one GEMM over pixel slots; -1 when the operands do not qualify
-int launch_conv_pw_gemm(infiniRocmRuntime_t rt, int dtype, const void *x, const void *w, const void *bias, const void *res, void *y,
-                        int64_t n, int64_t c, int64_t hw, int64_t f, int act);
-} // namespace irocm
+// problem -> ConvProblem with the reference's output size (src/operators/conv.cc:98-101)
+static ConvProblem conv_problem(int64_t n, int64_t c, int64_t h, int64_t wd, int64_t f, int64_t r, int64_t s, int ph, int pw, int sh, int sw,
+                                int dh, int dw, int64_t groups, int act, bool residual) {
+    ConvProblem q = {n, c, h, wd, f, (int)r, (int)s, ph, pw, sh, sw, dh, dw, groups, 0, 0, act, residual};
+    q.oh = (int)((h - (r - sh) * dh + 2 * ph) / sh);
+    q.ow = (int)((wd - (s - sw) * dw + 2 * pw) / sw);
+    return q;
+}
+
+// status of conv2d's argument checks (shared with the route query, which has no tensors)
+static int conv_check_args(int dtype, int64_t n, int64_t c, int64_t h, int64_t wd, int64_t f, int64_t r, int64_t s, int ph, int pw, int sh,
+                           int sw, int dh, int dw, int64_t groups, int act) {
+    IROCM_CHECK_ARG(dtype == INFINI_DT_F32 || dtype == INFINI_DT_F16 || dtype == INFINI_DT_BF16,
+                    "conv2d: unsupported dtype %s", dtype_name(dtype));
+    IROCM_CHECK_ARG(n >= 0 && c > 0 && h > 0 && wd > 0 && f > 0 && r > 0 && s > 0, "conv2d: bad extent");
+    IROCM_CHECK_ARG(groups > 0 && c % groups == 0 && f % groups == 0, "conv2d: groups %lld do not divide C=%lld / F=%lld",
+                    (long long)groups, (long long)c, (long long)f);
+    IROCM_CHECK_ARG(sh > 0 && sw > 0 && dh > 0 && dw > 0 && ph >= 0 && pw >= 0, "conv2d: bad attributes");
+    IROCM_CHECK_ARG(act >= 0 && act <= 3, "conv2d: bad act %d", act);
+    const ConvProblem q = conv_problem(n, c, h, wd, f, r, s, ph, pw, sh, sw, dh, dw, groups, act, false);
+    IROCM_CHECK_ARG(q.oh > 0 && q.ow > 0, "conv2d: empty output %dx%d", q.oh, q.ow);
+    IROCM_CHECK_ARG((long)r * s < 4096, "conv2d: kernel window too large");
+    return INFINI_ROCM_OK;
+}
 
 extern "C" {
 
@@ -462,120 +471,63 @@ int infini_rocm_conv2d_res(infiniRocmRuntime_t rt, int dtype, const void *x, con
                            const void *residual, void *y, int64_t n, int64_t c, int64_t h, int64_t wd, int64_t f, int64_t r,
                            int64_t s, int ph, int pw, int sh, int sw, int dh, int dw, int64_t groups, int act) {
     IROCM_CHECK_ARG(rt, "NULL runtime");
-    IROCM_CHECK_ARG(dtype == INFINI_DT_F32 || dtype == INFINI_DT_F16 || dtype == INFINI_DT_BF16,
-                    "conv2d: unsupported dtype %s", dtype_name(dtype));
-    IROCM_CHECK_ARG(n >= 0 && c > 0 && h > 0 && wd > 0 && f > 0 && r > 0 && s > 0, "conv2d: bad extent");
-    IROCM_CHECK_ARG(groups > 0 && c % groups == 0 && f % groups == 0, "conv2d: groups %lld do not divide C=%lld / F=%lld",
-                    (long long)groups, (long long)c, (long long)f);
-    IROCM_CHECK_ARG(sh > 0 && sw > 0 && dh > 0 && dw > 0 && ph >= 0 && pw >= 0, "conv2d: bad attributes");
-    IROCM_CHECK_ARG(act >= 0 && act <= 3, "conv2d: bad act %d", act);
+    if (const int st = conv_check_args(dtype, n, c, h, wd, f, r, s, ph, pw, sh, sw, dh, dw, groups, act); st != INFINI_ROCM_OK)
+        return st;
+    if (n == 0)
+        return INFINI_ROCM_OK;
+    IROCM_CHECK_ARG(x && w && y, "conv2d: NULL tensor");
+    const ConvProblem q = conv_problem(n, c, h, wd, f, r, s, ph, pw, sh, sw, dh, dw, groups, act, residual != nullptr);
+    const ConvHooks hk = conv_hooks();
+    const ConvPlan plan = conv_plan(q, dtype, rt->conv_variant, rt->num_cu, hk, (int64_t)infiniRocmRuntime::kSyncFlagWords);
+    for (int i = 0; i < plan.count; ++i) {
+        int st = -1; // -1: the launcher declined (alignment, 32-bit offsets, slack around a tensor) — next candidate
+        switch (plan.cand[i]) {
+        case kRouteBatchedGemm32: // one fp32 GEMM per image, zero copy
+            if (((((uintptr_t)x) | ((uintptr_t)w) | ((uintptr_t)y)) & 15) != 0)
+                break;
+            [[fallthrough]];
+        case kRouteBatchedGemm:
+            rt->last_conv_route = conv_route_name(plan.cand[i]);
+            return infini_rocm_matmul(rt, dtype, w, x, bias, y, n, f, q.npix(), c, 0, 0, 0, c * q.npix(), 0, bias ? 1 : 0, 0, act);
+        case kRouteIgemm32:
+            rt->last_conv_route = conv_route_name(kRouteIgemm32); // ("igemm32_splitk" when the launcher splits K)
+            st = launch_conv_igemm32(rt, x, w, bias, residual, y, n, c, h, wd, f, q.r, q.s, ph, pw, sh, sw, dh, dw, q.oh, q.ow, act, hk);
+            break;
+        case kRouteDepthwise:
+            st = launch_conv_depthwise(rt, dtype, x, w, bias, y, n, c, h, wd, f, q.r, q.s, ph, pw, sh, sw, q.oh, q.ow, act);
+            break;
+        case kRoutePixelGemm:
+            st = launch_conv_pw_gemm(rt, dtype, x, w, bias, residual, y, n, c, q.npix(), f, act, hk);
+            break;
+        default: // kRouteTapShifted: the conv_s1.hip family
+            st = launch_conv_s1(rt, dtype, x, w, bias, residual, y, q, plan.s1, hk);
+            break;
+        }
+        if (st >= 0)
+            return st;
+    }
+    // the kernels that serve everything: conv_igemm16 (128 x 128 x 32 implicit GEMM) / conv_direct32 (fp32, one output per thread)
     ConvArgs p;
     p.x = x; p.w = w; p.bias = bias; p.res = residual; p.y = y;
-    p.n = (int)n; p.c = (int)c; p.h = (int)h; p.wd = (int)wd; p.f = (int)f; p.r = (int)r; p.s = (int)s;
+    p.n = (int)n; p.c = (int)c; p.h = (int)h; p.wd = (int)wd; p.f = (int)f; p.r = q.r; p.s = q.s;
     p.ph = ph; p.pw = pw; p.sh = sh; p.sw = sw; p.dh = dh; p.dw = dw;
     p.groups = (int)groups; p.cg = (int)(c / groups); p.fg = (int)(f / groups);
-    // reference output size: src/operators/conv.cc:98-101
-    p.oh = (int)((h - (r - sh) * dh + 2 * ph) / sh);
-    p.ow = (int)((wd - (s - sw) * dw + 2 * pw) / sw);
-    IROCM_CHECK_ARG(p.oh > 0 && p.ow > 0, "conv2d: empty output %dx%d", p.oh, p.ow);
+    p.oh = q.oh; p.ow = q.ow;
     p.kdim = p.cg * p.r * p.s;
     p.npix = p.oh * p.ow;
     p.act = act;
     p.magic_s = (65536u + (unsigned)s - 1) / (unsigned)s;
-    IROCM_CHECK_ARG((long)p.r * p.s < 4096, "conv2d: kernel window too large");
-    if (n == 0)
-        return INFINI_ROCM_OK;
-    IROCM_CHECK_ARG(x && w && y, "conv2d: NULL tensor");
-
+    p.tiles_m = (int)ceil_div(p.fg, 128);
+    p.tiles_p = (int)ceil_div(p.npix, 128);
     if (dtype == INFINI_DT_F32) {
-        // Round 5: fp32 convolutions on the fp32 matrix instruction (v_mfma_f32_32x32x2_f32: exact products and sums at 157 TF/s): every
-        // groups == 1 layer is the implicit GEMM of gemm32.hip (columns run across images; K rows that are not a multiple of 4 floats —
-        // the 3-channel stem — are copied into padded rows). Unit-stride pointwise layers were first routed to the fp32 tile GEMM as
-        // one GEMM per image (zero copy, "batched_gemm32"): measured at batch 32 the implicit GEMM with 64 x 64 tiles is faster on every
-        // ResNet-50 layer but one (C64 -> 64 @ 56^2: 25.5 vs 69 us; C1024 -> 256 @ 14^2: 52.9 vs 101; C512 -> 256 @ 28^2: 82.6 vs 79.8) —
-        // per-image GEMMs leave 23 % of a 14^2 / 7^2 plane's tiles empty and launch few workgroups; IROCM_CONV32_PW_BATCHED keeps that
-        // route for A/B. conv variant 1 keeps the one-output-per-thread kernel (A/B, tests); so do grouped layers and unaligned operands.
-        if (groups == 1 && rt->conv_variant != 1) {
-            if (r == 1 && s == 1 && ph == 0 && pw == 0 && sh == 1 && sw == 1 && dh == 1 && dw == 1 && !residual && p.npix % 4 == 0 && c % 4 == 0 &&
-                ((((uintptr_t)x) | ((uintptr_t)w) | ((uintptr_t)y)) & 15) == 0 && (long)n * f * p.npix < (1l << 31) &&
-                getenv("IROCM_CONV32_PW_BATCHED")) {
-                rt->last_conv_route = "batched_gemm32";
-                return infini_rocm_matmul(rt, dtype, w, x, bias, y, n, f, p.npix, c, 0, 0, 0, (int64_t)c * p.npix, 0, bias ? 1 : 0, 0, act);
-            }
-            rt->last_conv_route = "igemm32"; // ("igemm32_splitk" when the launcher splits K)
-            const int st = launch_conv_igemm32(rt, x, w, bias, residual, y, n, c, h, wd, f, (int)r, (int)s, ph, pw, sh, sw, dh, dw, p.oh, p.ow, act);
-            if (st >= 0)
-                return st;
-        }
         const long total = (long)n * f * p.npix;
         long g = ceil_div(total, 256);
         if (g > (long)rt->num_cu * 32) g = (long)rt->num_cu * 32;
         hipLaunchKernelGGL(conv_direct32, dim3((unsigned)g), dim3(256), 0, rt->stream, p);
         IROCM_LAUNCH_CHECK("conv_direct32");
-        rt->last_conv_route = "direct32";
+        rt->last_conv_route = conv_route_name(kRouteDirect32);
         return INFINI_ROCM_OK;
     }
-    const int variant = rt->conv_variant;
-    // Round 5: depthwise layers (groups == C: one input channel per filter) have their own HBM-bound kernel (conv_dw.hip); variant 1
-    // keeps the generic implicit GEMM (A/B, tests)
-    if (groups == c && groups > 1 && dh == 1 && dw == 1 && !residual && variant != 1) {
-        const int st = launch_conv_depthwise(rt, dtype, x, w, bias, y, n, c, h, wd, f, (int)r, (int)s, ph, pw, sh, sw, p.oh, p.ow, act);
-        if (st >= 0)
-            return st;
-    }
-    const bool same_s1 = sh == 1 && sw == 1 && dh == 1 && dw == 1 && groups == 1 && p.oh == p.h && p.ow == p.wd;
-    // Round 3: a unit-stride pointwise layer with >= 256 filters is ONE GEMM  Y[f][slot] = W[f][c] X[c][slot]  over pixel slots
-    // (image, pixel) on the persistent 256-row kernels in conv mode (gemm256p_kernel.h, CONV): LDS-DMA staging of both operands,
-    // tiles that span images (14 x 14 and 7 x 7 planes do not waste tiles), per-filter bias, residual and activation in the epilogue,
-    // NCHW stores. As plain GEMMs these layers run 1.2-1.8 x faster on that machinery than on the register-staged tap-shifted
-    // kernel (tools/probes/conv_as_gemm.py, profiles/r03_conv_as_gemm.txt); with fewer filters the 256-row tile is mostly empty
-    // and the old kernels win. Variant 5 forces it for every eligible shape.
-    if ((variant < 0 || variant == 5) && r == 1 && s == 1 && ph == 0 && pw == 0 && same_s1 && c % 64 == 0 && (act == 0 || act == 1) &&
-        // (>= 128 filters: C256->F128 @56x56 78 vs 100 us, C512->F128 @28x28 33 vs 40; with 64 the 256-row tile is 3/4 empty:
-        // 69 vs 60 us. The grid may be thin — C1024->F256 @14x14 is 100 tiles of 256^2 and still 22.6 vs 31.1 us, C2048->F512 @7x7
-        // 50 tiles and 38.8 vs 45.1 — but below ~3/16 of the CUs the 128 x 128 tiles of the tap-shifted kernel spread better.)
-        ((f >= 128 && ceil_div(f, 256) * ceil_div(n * ((p.npix + 7) / 8 * 8), 256) * 16 >= rt->num_cu * 3) || variant == 5)) {
-        const int st = launch_conv_pw_gemm(rt, dtype, x, w, bias, residual, y, n, c, p.npix, f, act);
-        if (st >= 0)
-            return st;
-    }
-    const bool pointwise_gemm = r == 1 && s == 1 && ph == 0 && pw == 0 && same_s1 && (p.npix % 8 == 0) && c % 64 == 0;
-    // big-plane pointwise layers with >= 256 filters and channels are plain batched GEMMs (LDS-DMA kernels); everything else whose
-    // output extent is ceil(input / stride) goes to the tap-shifted implicit GEMM of conv_s1.hip (measured per
-    // ResNet-50 layer with tools/conv_bench.py)
-    // a single K-step leaves nothing to pipeline: the small generic tile (more workgroups per CU) hides the latency better
-    const bool one_kstep = (long)c * r * s <= 64 && f >= 128;
-    // (an earlier rule sent 56x56 pointwise layers with >= 128 filters and <= 256 channels to the small generic tile; since the
-    // LDS-staged epilogue conv_s1 wins there too: C256->F128 @56x56 93 vs 112 us)
-    const bool big_plane_pointwise = false;
-    // conv_pw_kernel (conv_s1.hip) candidates; IROCM_CONV_PW=2 (tuning hook) sends them there ahead of the two rules above
-    static const int pw_pref = getenv("IROCM_CONV_PW") ? atoi(getenv("IROCM_CONV_PW")) : 1;
-    const bool pw_shape = r == 1 && s == 1 && ph == 0 && pw == 0 && groups == 1 && c % 64 == 0 && c <= 256 && f > 64;
-    // measured (tools/conv_bench.py): with <= 128 input channels conv_pw wins everywhere (C64->F256 @56x56 64 vs 89 us generic,
-    // C128->F512 @28x28 44 vs 59 us conv_s1); at C = 256 its 100 KiB of LDS leaves one workgroup per CU and it loses
-    const bool pw_default = pw_pref >= 1 && pw_shape && c <= 128 && p.npix % 2 == 0 && sh == 1 && sw == 1;
-    if (variant < 0 && (one_kstep || big_plane_pointwise) && !(pw_default || (pw_pref == 2 && pw_shape)))
-        goto generic;
-    if (groups == 1 && variant != 1 && !(variant == 3 && pointwise_gemm) &&
-        // batched-GEMM route by default only for long-K pointwise layers on big planes: with K <= 512 its 256^2 tiles run 8
-        // K-tiles each and the per-tile prologue + epilogue dominates (C512->F256 @28x28: 88 us vs 66 us on conv_s1)
-        (variant == 2 || variant == 4 || variant == 6 || variant == 7 || residual || !(pointwise_gemm && f >= 256 && c >= 1024 && p.npix >= 2048))) {
-        rt->last_conv_route = "tap_shifted";
-        const int st = launch_conv_s1(rt, dtype, x, w, bias, residual, y, (int)n, (int)c, (int)h, (int)wd, (int)f, (int)r, (int)s,
-                                      ph, pw, sh, sw, dh, dw, p.oh, p.ow, act);
-        if (st >= 0)
-            return st;
-    }
-    // pointwise convolution == batched GEMM  Y[n] = W[F x C] . X[n][C x HW]  (A broadcast over batch)
-    if (variant != 1 && !residual && r == 1 && s == 1 && ph == 0 && pw == 0 && sh == 1 && sw == 1 && groups == 1 && (p.npix % 8 == 0) &&
-        c % 64 == 0) {
-        rt->last_conv_route = "batched_gemm";
-        return infini_rocm_matmul(rt, dtype, w, x, bias, y, n, f, p.npix, c, 0, 0, 0, (int64_t)c * p.npix,
-                                  0, bias ? 1 : 0, 0, act);
-    }
-generic:
-    p.tiles_m = (int)ceil_div(p.fg, 128);
-    p.tiles_p = (int)ceil_div(p.npix, 128);
     const long blocks = (long)n * groups * p.tiles_m * p.tiles_p;
     IROCM_CHECK_ARG(blocks < (1l << 31), "conv2d: too many tiles");
     if (dtype == INFINI_DT_BF16)
@@ -583,7 +535,22 @@ generic:
     else
         hipLaunchKernelGGL(conv_igemm16<F16Traits>, dim3((unsigned)blocks), dim3(256), 0, rt->stream, p);
     IROCM_LAUNCH_CHECK("conv_igemm16");
-    rt->last_conv_route = "generic";
+    rt->last_conv_route = conv_route_name(kRouteGeneric);
+    return INFINI_ROCM_OK;
+}
+
+int infini_rocm_conv2d_plan_route(int dtype, int64_t n, int64_t c, int64_t h, int64_t wd, int64_t f, int64_t r, int64_t s, int ph, int pw,
+                                  int sh, int sw, int dh, int dw, int64_t groups, int act, int has_residual, int variant, int num_cu,
+                                  const char **route, const char **form) {
+    IROCM_CHECK_ARG(route && form, "NULL argument");
+    IROCM_CHECK_ARG(variant >= -1 && variant <= 7 && num_cu > 0, "conv2d: bad variant %d / CU count %d", variant, num_cu);
+    if (const int st = conv_check_args(dtype, n, c, h, wd, f, r, s, ph, pw, sh, sw, dh, dw, groups, act); st != INFINI_ROCM_OK)
+        return st;
+    const ConvProblem q = conv_problem(n, c, h, wd, f, r, s, ph, pw, sh, sw, dh, dw, groups, act, has_residual != 0);
+    const ConvHooks hk = conv_hooks();
+    ConvForm fm = kFormNone;
+    *route = conv_route_name(conv_plan_first(conv_plan(q, dtype, variant, num_cu, hk, (int64_t)infiniRocmRuntime::kSyncFlagWords), dtype, hk, &fm));
+    *form = conv_form_name(fm);
     return INFINI_ROCM_OK;
 }
 

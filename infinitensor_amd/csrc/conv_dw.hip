@@ -18,6 +18,7 @@
 // is set up once. (Version 1 of this file staged rows through LDS and decoded one item per 8 outputs: 4.5 VALU-issue cycles per
 // instruction with 78 % of the instructions overhead — 0.12-0.35 of the HBM peak.)
 #include "gemm256_common.h" // (sfor: compile-time loops)
+#include "conv_internal.h"
 #include <algorithm>
 
 namespace irocm {
@@ -204,7 +205,7 @@ template <typename Tr, int R, int S> static int launch_dw(infiniRocmRuntime_t rt
 // Returns -1 when the layer does not qualify (the caller takes the generic kernel), a status otherwise.
 int launch_conv_depthwise(infiniRocmRuntime_t rt, int dtype, const void *x, const void *w, const void *bias, void *y, int64_t n, int64_t c,
                           int64_t h, int64_t wd, int64_t f, int r, int s, int ph, int pw, int sh, int sw, int oh, int ow, int act) {
-    if (!((r == 3 && s == 3) || (r == 5 && s == 5)) || !(sh == 1 || sh == 2) || sh != sw || f % c != 0)
+    if (!conv_dw_window(r, s, sh, sw, f, c))
         return -1;
     if (ph < 0 || pw < 0 || (((uintptr_t)x) & 1) || (((uintptr_t)y) & 1))
         return -1;
@@ -256,7 +257,7 @@ int launch_conv_depthwise(infiniRocmRuntime_t rt, int dtype, const void *x, cons
     }
     if (getenv("IROCM_DW_SAFE")) // test hook (read per call): the tensor-exact form
         fast = false;
-    rt->last_conv_route = "depthwise";
+    rt->last_conv_route = conv_route_name(kRouteDepthwise);
     if (dtype == INFINI_DT_BF16)
         return r == 3 ? launch_dw<Bf16Traits, 3, 3>(rt, p, fast) : launch_dw<Bf16Traits, 5, 5>(rt, p, fast);
     return r == 3 ? launch_dw<F16Traits, 3, 3>(rt, p, fast) : launch_dw<F16Traits, 5, 5>(rt, p, fast);

@@ -29,21 +29,11 @@
 //     3x3/2); on a phase plane every tap is again a constant shift of a unit-stride same-size access, so the same
 //     kernel runs with a per-tap (plane, shift) pair. Needs OH == ceil(H / sh) and OW == ceil(W / sw).
 #include "gemm256_common.h"
+#include "conv_internal.h"
+#include <algorithm>
 #include <type_traits>
-#include <cstdlib>
 
 namespace irocm {
-// gemm256p_conv.hip
-int launch_conv_pw_gemm(infiniRocmRuntime_t rt, int dtype, const void *x, const void *w, const void *bias, const void *res, void *y,
-                        int64_t n, int64_t c, int64_t hw, int64_t f, int act);
-} // namespace irocm
-
-namespace irocm {
-
-int launch_conv_tap_gemm(infiniRocmRuntime_t rt, int dtype, const void *x, const void *wp, const void *bias, void *y, int64_t n,
-                         int64_t c, int oh, int ow, int in_h, int in_w, int stride, int64_t plane_elems, int64_t f, int act,
-                         int split, void *slab, size_t slab_bytes);
-int conv_tap_split(infiniRocmRuntime_t rt, int64_t n, int64_t hw, int64_t c, int64_t f, size_t *slab_bytes);
 
 template <int N> __device__ __forceinline__ void g256p_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
@@ -1573,7 +1563,7 @@ template <typename Tr> static int launch_resident(infiniRocmRuntime_t rt, ConvS1
     const int grid = ntiles < rt->num_cu ? ntiles : rt->num_cu;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, rt->stream, p, halo8, pslots, ntiles);
     IROCM_LAUNCH_CHECK("conv_resident");
-    rt->last_conv_route = "resident";
+    rt->last_conv_route = conv_route_name(kRouteResident);
     return INFINI_ROCM_OK;
 }
 
@@ -1627,74 +1617,41 @@ static int launch_s1(infiniRocmRuntime_t rt, ConvS1Args &p) {
     return INFINI_ROCM_OK;
 }
 
-// Returns -1 when the shape is not a conv_s1 shape (caller falls through to the generic kernel).
-int launch_conv_s1(infiniRocmRuntime_t rt, int dtype, const void *x, const void *w, const void *bias, const void *res,
-                   void *y, int n, int c, int h, int wd, int f, int r, int s, int ph, int pw, int sh, int sw, int dh, int dw,
-                   int oh, int ow, int act) {
-    if (r > 7 || s > 7 || ((uintptr_t)w & 15) != 0 || ((uintptr_t)x & 3) != 0)
-        return -1;
-    const bool rowtap = c % 32 != 0;
-    if (rowtap && (((long)c * r * s + 31) & ~31l) > 2048)
-        return -1; // the per-k LDS table holds 2048 entries
-    if (sh * sw > 16 || oh != (h + sh - 1) / sh || ow != (wd + sw - 1) / sw)
-        return -1;
-    ConvS1Args p;
+// ---- launch_conv_s1: arguments -> workspace -> packed weights -> phase planes -> the planned kernel -------------------------------
+
+// Kernel arguments and the phases some tap reads. false: the activation does not fit 32-bit buffer offsets (decline).
+static bool fill_args(ConvS1Args &p, PhaseSplitArgs &ps, const void *x, const void *w, const void *bias, const void *res, void *y,
+                      const ConvProblem &q, const ConvS1Plan &plan, const ConvHooks &hk) {
     p.x = x; p.w = w; p.bias = bias; p.res = res; p.y = y;
-    p.nimg = n; p.c = c; p.f = f; p.r = r; p.s = s; p.ph = ph; p.pw = pw;
-    p.sh = sh; p.sw = sw; p.dh = dh; p.dw = dw;
-    p.in_h = h; p.in_w = wd; p.h = oh; p.wd = ow;
-    p.hw = oh * ow;
+    p.nimg = (int)q.n; p.c = (int)q.c; p.f = (int)q.f; p.r = q.r; p.s = q.s; p.ph = q.ph; p.pw = q.pw;
+    p.sh = q.sh; p.sw = q.sw; p.dh = q.dh; p.dw = q.dw;
+    p.in_h = (int)q.h; p.in_w = (int)q.w; p.h = q.oh; p.wd = q.ow;
+    p.hw = q.oh * q.ow;
     p.hwp = (p.hw + 7) & ~7;
     p.hwp_m = divmod_magic(p.hwp);
-    p.wd_m = divmod_magic(ow);
-    if ((long)n * p.hwp >= (1l << 31))
-        return -1;
-    p.ncols = n * p.hwp;
-    p.act = act;
-    static const int wide = getenv("IROCM_CONV_WIDE") ? atoi(getenv("IROCM_CONV_WIDE")) : 2; // 0 off, 1 even planes only, 2 all
-    p.wide_epilogue = wide;
-    static const int epi_probe = getenv("IROCM_CONV_EPI_PROBE") ? atoi(getenv("IROCM_CONV_EPI_PROBE")) : 0;
-    p.epi_probe = epi_probe;
-    p.plane_elems = (long)n * c * p.hw;
-    {
-        const long yb = (long)n * f * p.hw * 2;
-        p.y_bytes = (yb < (1l << 31) - 64 && (((uintptr_t)res) & 3) == 0) ? (unsigned)yb : 0u; // else: the direct epilogue
-    }
-    // phases read by some tap
-    PhaseSplitArgs ps;
+    p.wd_m = divmod_magic(q.ow);
+    p.ncols = p.nimg * p.hwp; // (< 2^31: conv_s1_shape)
+    p.act = q.act;
+    p.wide_epilogue = hk.wide;
+    p.epi_probe = hk.epi_probe;
+    p.plane_elems = (long)q.n * q.c * p.hw;
+    p.kdim = p.c * q.r * q.s;
+    p.kpad = (p.kdim + 31) & ~31;
+    const long yb = (long)q.n * q.f * p.hw * 2;
+    p.y_bytes = (yb < (1l << 31) - 64 && (((uintptr_t)res) & 3) == 0) ? (unsigned)yb : 0u; // else: the direct epilogue
     ps.nslots = 0;
     for (int i = 0; i < 16; ++i)
         p.slot[i] = -1;
-    for (int rr = 0; rr < r; ++rr)
-        for (int ss = 0; ss < s; ++ss) {
-            const int py = ((rr * dh - ph) % sh + sh) % sh, px = ((ss * dw - pw) % sw + sw) % sw;
-            if (p.slot[py * sw + px] < 0) {
+    for (int rr = 0; rr < q.r; ++rr)
+        for (int ss = 0; ss < q.s; ++ss) {
+            const int py = ((rr * q.dh - q.ph) % q.sh + q.sh) % q.sh, px = ((ss * q.dw - q.pw) % q.sw + q.sw) % q.sw;
+            if (p.slot[py * q.sw + px] < 0) {
                 ps.py[ps.nslots] = (signed char)py;
                 ps.px[ps.nslots] = (signed char)px;
-                p.slot[py * sw + px] = (signed char)ps.nslots++;
+                p.slot[py * q.sw + px] = (signed char)ps.nslots++;
             }
         }
-    // Round 5: 3 x 3 / pad 1 layers of stride 1 or 2 with >= 256 filters as ONE GEMM with K = 9 C on the persistent 256-row kernels
-    // (gemm256p_kernel.h, CONV = 3: TAP mode; gemm256p_conv3.hip). Conv variant 7 forces it for every eligible shape (tests, tune(),
-    // tools/conv_bench.py). Default routing by measurement (batch 128, f16, us; tools/conv_bench.py on three boxes):
-    //   strided layers (the tap-shifted kernel on phase planes was their only kernel): C256 28 x 28 / 2 -> 74-77 vs 87-92,
-    //     C512 14 x 14 / 2 -> 78-82 vs 115-120 (split-K x 4): taken whenever F >= 256;
-    //   unit-stride layers compete with the patch kernels: C512 7 x 7 (56 tiles, split-K x 4) 58-61 vs 69-73: taken; C256 14 x 14 (100
-    //     tiles, split-K x 2) 51-57 vs 49.5: not taken — i.e. only where the tiles are so few that the split is by four.
-    const bool tap_shape = r == 3 && s == 3 && ph == 1 && pw == 1 && dh == 1 && dw == 1 && ((sh == 1 && sw == 1) || (sh == 2 && sw == 2)) &&
-                           c % 64 == 0 && !res && (act == 0 || act == 1) && (long)oh * ow >= 8;
-    static const int tap_on = getenv("IROCM_CONV_TAP") ? atoi(getenv("IROCM_CONV_TAP")) : 1; // A/B hook: 0 = off
-    bool tap_want = tap_shape && rt->conv_variant == 7;
-    // (strided layers from 128 filters on: half of the 256-row tile is empty there, and the tap GEMM still beats the phase-plane
-    // tap-shifted kernel — C128 -> 128 @56^2 / 2 at batch 128: 98.2 vs 104.7 us; unit-stride layers need the 256 filters)
-    if (tap_shape && rt->conv_variant < 0 && tap_on && (f >= 256 || (sh == 2 && f >= 128))) {
-        const long tiles256 = ceil_div(f, 256) * ceil_div((long)n * (((long)oh * ow + 7) / 8 * 8), 256);
-        if (sh == 2)
-            tap_want = tiles256 * 4 >= rt->num_cu / 2;                       // enough work for the persistent kernels at all
-        else
-            tap_want = conv_tap_split(rt, n, (long)oh * ow, c, f, nullptr) >= 4; // few tiles, long K
-    }
-    if (tap_want && sh == 2) { // the tap mode addresses the phase planes in the fixed order py * 2 + px
+    if (plan.tap && q.sh == 2) { // the tap mode addresses the phase planes in the fixed order py * 2 + px
         ps.nslots = 4;
         for (int i = 0; i < 4; ++i) {
             p.slot[i] = (signed char)i;
@@ -1702,213 +1659,179 @@ int launch_conv_s1(infiniRocmRuntime_t rt, int dtype, const void *x, const void 
             ps.px[i] = (signed char)(i & 1);
         }
     }
-    const bool split = sh * sw > 1;
-    const long x_bytes = p.plane_elems * 2 * (split ? ps.nslots : 1);
+    const long x_bytes = p.plane_elems * 2 * (q.sh * q.sw > 1 ? ps.nslots : 1);
     if (x_bytes >= (1l << 31) - 64 || x_bytes < 64) // 32-bit buffer offsets; `x_bytes - 16` must not wrap
-        return -1;
+        return false;
     p.x_bytes = (unsigned)x_bytes;
-    // Re-packed weights: FCRS -> [RS][F][C] (or [F][Kpad] for ROWTAP). When the caller declared the weights constant
-    // (infini_rocm_conv2d_set_const_weights: the plugin does for graph weights / inputs no operator writes) the packed
-    // image is built ONCE, kept in a runtime-owned buffer keyed by (pointer, F, C, RS, layout) and dropped when anything
-    // is copied over the source range (runtime.hip) — the reference's cuDNN path has no per-call weight transform either
-    // (src/kernels/cuda/conv.cc:143-168). Otherwise it is rebuilt per call in the workspace: [ weights | phase planes ].
-    p.kdim = c * r * s;
-    p.kpad = (p.kdim + 31) & ~31;
-    const size_t w_bytes = rowtap ? (((size_t)f * p.kpad * 2 + 255) & ~(size_t)255)
-                                  : (r * s > 1 ? (((size_t)f * c * r * s * 2 + 255) & ~(size_t)255) : 0);
-    const bool cached = w_bytes && rt->conv_const_weights;
-    const void *packed = nullptr;
+    return true;
+}
+
+// Re-packed weights: FCRS -> [RS][F][C] (or [F][Kpad] for ROWTAP). When the caller declared the weights constant
+// (infini_rocm_conv2d_set_const_weights: the plugin does for graph weights / inputs no operator writes) the packed
+// image is built ONCE, kept in a runtime-owned buffer keyed by (pointer, F, C, RS, layout) and dropped when anything
+// is copied over the source range (runtime.hip) — the reference's cuDNN path has no per-call weight transform either
+// (src/kernels/cuda/conv.cc:143-168). Otherwise it is rebuilt per call at `ws_dst` in the workspace. *image: what the kernels read.
+static int pack_weights(infiniRocmRuntime_t rt, const void *w, const ConvS1Args &p, bool rowtap, size_t w_bytes, bool cached, void *ws_dst,
+                        const void **image) {
+    const int rs = p.r * p.s;
     hipStream_t pack_stream = rt->stream; // (may be the legacy default stream, i.e. a null handle: never test it)
-    bool need_pack = w_bytes != 0;
+    void *dst = ws_dst;
     if (cached) {
-        packed = wcache_lookup(rt, w, f, c, r * s, rowtap ? 1 : 0);
-        if (!packed) {
-            void *buf = nullptr;
-            int st = wcache_insert(rt, w, (size_t)f * c * r * s * 2, f, c, r * s, rowtap ? 1 : 0, w_bytes, &buf, &pack_stream);
-            if (st != INFINI_ROCM_OK)
-                return st;
-            packed = buf;
-        } else {
-            need_pack = false; // hit: nothing to launch
-        }
-    }
-    const size_t ws_w = cached ? 0 : w_bytes;
-    // the tap GEMM's split-K exchange slab (fp32 partial row blocks) sits behind the weights / phase planes
-    size_t tap_slab_bytes = 0;
-    const int tap_split = tap_want ? conv_tap_split(rt, n, (long)oh * ow, c, f, &tap_slab_bytes) : 1;
-    // (+256: the pixel-slot GEMM a strided pointwise layer continues with reads up to 14 bytes past a ragged last plane)
-    const size_t ws_planes = ws_w + (split ? (size_t)x_bytes + 256 : 0);
-    const size_t ws_slab_off = (ws_planes + 255) & ~(size_t)255;
-    const size_t ws_bytes = tap_slab_bytes ? ws_slab_off + tap_slab_bytes : ws_planes;
-    char *ws = nullptr;
-    if (ws_bytes) {
-        int st = infini_rocm_workspace(rt, ws_bytes, (void **)&ws);
+        if ((*image = wcache_lookup(rt, w, p.f, p.c, rs, rowtap ? 1 : 0)) != nullptr)
+            return INFINI_ROCM_OK; // hit: nothing to launch
+        const int st = wcache_insert(rt, w, (size_t)p.f * p.c * rs * 2, p.f, p.c, rs, rowtap ? 1 : 0, w_bytes, &dst, &pack_stream);
         if (st != INFINI_ROCM_OK)
             return st;
     }
-    unsigned short *wdst = cached ? (unsigned short *)const_cast<void *>(packed) : (unsigned short *)ws;
-    if (need_pack) {
-        // a cache entry published by wcache_insert above must not outlive a failed pack: the next conv with the same key
-        // would hit it and read an uninitialised image
-        auto fail_pack = [&](const char *what, hipError_t e) {
-            if (cached)
-                wcache_forget(rt, packed);
-            IROCM_FAIL(INFINI_ROCM_HIP_ERROR, "launch of %s failed: %s", what, hipGetErrorString(e));
-        };
-        if (rowtap) { // FCRS -> [F][Kpad], k = tap * C + c
-            long g = ceil_div((long)f * p.kpad, 256);
-            if (g > 4096) g = 4096;
-            hipLaunchKernelGGL(conv_repack_w_flat, dim3((unsigned)g), dim3(256), 0, pack_stream, (const unsigned short *)w, wdst, f,
-                               c, r * s, p.kpad);
-            if (hipError_t e = hipGetLastError(); e != hipSuccess)
-                return fail_pack("conv_repack_w_flat", e);
-        } else { // FCRS -> [RS][F][C]
-            long g = ceil_div((long)f * c * r * s, 256);
-            if (g > 4096) g = 4096;
-            hipLaunchKernelGGL(conv_repack_w, dim3((unsigned)g), dim3(256), 0, pack_stream, (const unsigned short *)w, wdst, f, c,
-                               r * s);
-            if (hipError_t e = hipGetLastError(); e != hipSuccess)
-                return fail_pack("conv_repack_w", e);
-        }
-        if (cached) {
-            int st = wcache_commit(rt, pack_stream);
-            if (st != INFINI_ROCM_OK) {
-                wcache_forget(rt, packed);
-                return st;
-            }
-        }
-    }
-    if (w_bytes)
-        p.w = wdst;
-    const size_t w_off = ws_w;
-    if (split) {
-        ps.x = (const unsigned short *)x;
-        ps.o = (unsigned short *)(ws + w_off);
-        ps.planes = (long)n * c;
-        ps.in_h = h; ps.in_w = wd; ps.oh = oh; ps.ow = ow; ps.sh = sh; ps.sw = sw;
-        const long work2 = (long)n * c * 2 * oh * ((ow + 1) / 2);
-        // vector kernels: 8 columns per thread when the row length allows (any phase set), else the quad kernel when all
-        // four phases are wanted (3x3/2, 7x7/2); a 1x1/2 on odd-sized rows reads one phase and is faster element-wise
-        const bool v8ok = wd % 8 == 0 && (((uintptr_t)x) & 15) == 0 && (w_off % 8 == 0) && (p.plane_elems % 4 == 0);
+    *image = dst;
+    long g = ceil_div(rowtap ? (long)p.f * p.kpad : (long)p.f * p.c * rs, 256);
+    if (g > 4096) g = 4096;
+    if (rowtap) // FCRS -> [F][Kpad], k = tap * C + c
+        hipLaunchKernelGGL(conv_repack_w_flat, dim3((unsigned)g), dim3(256), 0, pack_stream, (const unsigned short *)w, (unsigned short *)dst,
+                           p.f, p.c, rs, p.kpad);
+    else // FCRS -> [RS][F][C]
+        hipLaunchKernelGGL(conv_repack_w, dim3((unsigned)g), dim3(256), 0, pack_stream, (const unsigned short *)w, (unsigned short *)dst, p.f,
+                           p.c, rs);
+    hipError_t e = hipGetLastError();
+    int st = INFINI_ROCM_OK;
+    if (e == hipSuccess && cached)
+        st = wcache_commit(rt, pack_stream);
+    // a cache entry published by wcache_insert must not outlive a failed pack: the next conv with the same key would hit it and read
+    // an uninitialised image
+    if (cached && (e != hipSuccess || st != INFINI_ROCM_OK))
+        wcache_forget(rt, dst);
+    if (e != hipSuccess)
+        IROCM_FAIL(INFINI_ROCM_HIP_ERROR, "launch of %s failed: %s", rowtap ? "conv_repack_w_flat" : "conv_repack_w", hipGetErrorString(e));
+    return st;
+}
+
+// De-interleaves x into the phase planes `ps` lists (slot order of p.slot), at `o`. Vector kernels: 8 columns per thread when the row
+// length allows (any phase set), else the quad kernel when all four phases are wanted (3x3/2, 7x7/2); a 1x1/2 on odd-sized rows
+// reads one phase and is faster element-wise.
+static int split_phases(infiniRocmRuntime_t rt, const ConvS1Args &p, PhaseSplitArgs &ps, const void *x, unsigned short *o) {
+    const int n = p.nimg, c = p.c, h = p.in_h, wd = p.in_w, oh = p.h, ow = p.wd;
+    const long cap = (long)rt->num_cu * 32; // grid-stride kernels: at most 32 workgroups per CU
+    const bool s2 = p.sh == 2 && p.sw == 2;
+    ps.x = (const unsigned short *)x;
+    ps.o = o;
+    ps.planes = (long)n * c;
+    ps.in_h = h; ps.in_w = wd; ps.oh = oh; ps.ow = ow; ps.sh = p.sh; ps.sw = p.sw;
+    const long work2 = (long)n * c * 2 * oh * ((ow + 1) / 2);
+    const bool v8ok = wd % 8 == 0 && (((uintptr_t)x) & 15) == 0 && (p.plane_elems % 4 == 0);
+    const int vec = wd % 8 == 0 ? 8 : (wd % 4 == 0 ? 4 : (wd % 2 == 0 ? 2 : 0));
+    if (s2 && ps.nslots == 1 && ps.py[0] == 0 && ps.px[0] == 0 && vec && (((uintptr_t)x) & 3) == 0 && (long)n * c * oh * (wd / vec) < (1l << 31)) {
         // one phase, (0, 0), of an even-width input (the 1 x 1 / 2 layers): the subsampling kernel
-        const int vec = wd % 8 == 0 ? 8 : (wd % 4 == 0 ? 4 : (wd % 2 == 0 ? 2 : 0));
-        if (sh == 2 && sw == 2 && ps.nslots == 1 && ps.py[0] == 0 && ps.px[0] == 0 && vec && (((uintptr_t)x) & 3) == 0 && (w_off % 4 == 0) &&
-            (long)n * c * oh * (wd / vec) < (1l << 31)) {
-            Subsample2Args sa;
-            sa.x = ps.x; sa.o = ps.o; sa.planes = n * c; sa.in_h = h; sa.in_w = wd; sa.oh = oh; sa.ow = ow;
-            sa.groups_m = divmod_magic(wd / vec);
-            sa.oh_m = divmod_magic(oh);
-            long g = ceil_div((long)n * c * oh * (wd / vec), 256);
-            if (g > (long)rt->num_cu * 32) g = (long)rt->num_cu * 32;
-            if (vec == 8) hipLaunchKernelGGL(conv_subsample2_kernel<8>, dim3((unsigned)g), dim3(256), 0, rt->stream, sa);
-            else if (vec == 4) hipLaunchKernelGGL(conv_subsample2_kernel<4>, dim3((unsigned)g), dim3(256), 0, rt->stream, sa);
-            else hipLaunchKernelGGL(conv_subsample2_kernel<2>, dim3((unsigned)g), dim3(256), 0, rt->stream, sa);
-        } else if (sh == 2 && sw == 2 && (ps.nslots == 4 || v8ok) && work2 + (long)rt->num_cu * 32 * 256 < (1l << 31)) {
-            PhaseSplit2Args a2;
-            a2.x = ps.x; a2.o = ps.o; a2.planes = n * c; a2.in_h = h; a2.in_w = wd; a2.oh = oh; a2.ow = ow;
-            a2.plane_elems = p.plane_elems;
-            for (int i = 0; i < 4; ++i)
-                a2.slot[i] = p.slot[i];
-            const bool v8 = wd % 8 == 0 && (((uintptr_t)a2.x) & 15) == 0 && (((uintptr_t)a2.o) & 7) == 0 &&
-                            (p.plane_elems % 4 == 0);
-            long g = ceil_div(v8 ? work2 / 2 : work2, 256);
-            if (g > (long)rt->num_cu * 32) g = (long)rt->num_cu * 32;
-            const int vn = v8 ? 0 : (wd % 4 == 0 && p.plane_elems % 2 == 0 ? 4 : (wd % 2 == 0 ? 2 : 0));
-            if (v8) {
-                hipLaunchKernelGGL(conv_phase_split_2x2_v8, dim3((unsigned)g), dim3(256), 0, rt->stream, a2);
-            } else if (vn && (((uintptr_t)a2.x) & 3) == 0 && (((uintptr_t)a2.o) & 3) == 0 && (long)n * c * 2 * oh * (wd / vn) < (1l << 31)) {
-                PhaseSplit2vArgs av;
-                av.a = a2;
-                av.groups_m = divmod_magic(wd / vn);
-                av.rows_m = divmod_magic(2 * oh);
-                long gv = ceil_div((long)n * c * 2 * oh * (wd / vn), 256);
-                if (gv > (long)rt->num_cu * 32) gv = (long)rt->num_cu * 32;
-                if (vn == 4) hipLaunchKernelGGL(conv_phase_split_2x2_vn<4>, dim3((unsigned)gv), dim3(256), 0, rt->stream, av);
-                else hipLaunchKernelGGL(conv_phase_split_2x2_vn<2>, dim3((unsigned)gv), dim3(256), 0, rt->stream, av);
-            } else {
-                hipLaunchKernelGGL(conv_phase_split_2x2, dim3((unsigned)g), dim3(256), 0, rt->stream, a2);
-            }
+        Subsample2Args sa;
+        sa.x = ps.x; sa.o = ps.o; sa.planes = n * c; sa.in_h = h; sa.in_w = wd; sa.oh = oh; sa.ow = ow;
+        sa.groups_m = divmod_magic(wd / vec);
+        sa.oh_m = divmod_magic(oh);
+        const unsigned g = (unsigned)std::min(ceil_div((long)n * c * oh * (wd / vec), 256), cap);
+        if (vec == 8) hipLaunchKernelGGL(conv_subsample2_kernel<8>, dim3(g), dim3(256), 0, rt->stream, sa);
+        else if (vec == 4) hipLaunchKernelGGL(conv_subsample2_kernel<4>, dim3(g), dim3(256), 0, rt->stream, sa);
+        else hipLaunchKernelGGL(conv_subsample2_kernel<2>, dim3(g), dim3(256), 0, rt->stream, sa);
+    } else if (s2 && (ps.nslots == 4 || v8ok) && work2 + cap * 256 < (1l << 31)) {
+        PhaseSplit2Args a2;
+        a2.x = ps.x; a2.o = ps.o; a2.planes = n * c; a2.in_h = h; a2.in_w = wd; a2.oh = oh; a2.ow = ow;
+        a2.plane_elems = p.plane_elems;
+        for (int i = 0; i < 4; ++i)
+            a2.slot[i] = p.slot[i];
+        const bool v8 = v8ok && (((uintptr_t)a2.o) & 7) == 0;
+        const unsigned g = (unsigned)std::min(ceil_div(v8 ? work2 / 2 : work2, 256), cap);
+        const int vn = v8 ? 0 : (wd % 4 == 0 && p.plane_elems % 2 == 0 ? 4 : (wd % 2 == 0 ? 2 : 0));
+        if (v8) {
+            hipLaunchKernelGGL(conv_phase_split_2x2_v8, dim3(g), dim3(256), 0, rt->stream, a2);
+        } else if (vn && (((uintptr_t)a2.x) & 3) == 0 && (((uintptr_t)a2.o) & 3) == 0 && (long)n * c * 2 * oh * (wd / vn) < (1l << 31)) {
+            PhaseSplit2vArgs av;
+            av.a = a2;
+            av.groups_m = divmod_magic(wd / vn);
+            av.rows_m = divmod_magic(2 * oh);
+            const unsigned gv = (unsigned)std::min(ceil_div((long)n * c * 2 * oh * (wd / vn), 256), cap);
+            if (vn == 4) hipLaunchKernelGGL(conv_phase_split_2x2_vn<4>, dim3(gv), dim3(256), 0, rt->stream, av);
+            else hipLaunchKernelGGL(conv_phase_split_2x2_vn<2>, dim3(gv), dim3(256), 0, rt->stream, av);
         } else {
-            long g = ceil_div(p.plane_elems * ps.nslots, 256);
-            if (g > (long)rt->num_cu * 32) g = (long)rt->num_cu * 32;
-            hipLaunchKernelGGL(conv_phase_split, dim3((unsigned)g), dim3(256), 0, rt->stream, ps);
+            hipLaunchKernelGGL(conv_phase_split_2x2, dim3(g), dim3(256), 0, rt->stream, a2);
         }
-        IROCM_LAUNCH_CHECK("conv_phase_split");
+    } else {
+        const unsigned g = (unsigned)std::min(ceil_div(p.plane_elems * ps.nslots, 256), cap);
+        hipLaunchKernelGGL(conv_phase_split, dim3(g), dim3(256), 0, rt->stream, ps);
+    }
+    IROCM_LAUNCH_CHECK("conv_phase_split");
+    return INFINI_ROCM_OK;
+}
+
+// The tap GEMM on the layer's own input: a tap moves a 16-byte run by up to one row + one pixel, and the bytes in front of and behind X
+// it then reaches (masked away, but fetched) must be readable memory. True inside an arena of infini_rocm_alloc (256 bytes of slack
+// on both sides) and for a tensor in the middle of a caller's block; a tensor at the very edge of its allocation takes the other kernels.
+static bool tap_reach_readable(const void *x, const ConvS1Args &p) {
+    const long reach = ((long)p.wd + 1) * 2 + 16;
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)x) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    const char *lo = (const char *)x - reach, *hi = (const char *)x + p.plane_elems * 2 + reach;
+    return lo >= (const char *)base && hi <= (const char *)base + size;
+}
+
+static int launch_form(infiniRocmRuntime_t rt, bool bf, ConvS1Args &p, ConvForm form, int halo8) {
+    rt->last_conv_route = conv_route_name(kRouteTapShifted); // (launch_resident names its own)
+    switch (form) {
+    case kFormPw: return bf ? launch_pw<Bf16Traits>(rt, p) : launch_pw<F16Traits>(rt, p);
+    case kFormRowtap: return bf ? launch_s1<Bf16Traits, 1, 4, 32, true>(rt, p) : launch_s1<F16Traits, 1, 4, 32, true>(rt, p);
+    case kFormPatchWide: return bf ? launch_patch<Bf16Traits, 2, 4>(rt, p, halo8, 256 + 2 * halo8) : launch_patch<F16Traits, 2, 4>(rt, p, halo8, 256 + 2 * halo8);
+    case kFormPatch: return bf ? launch_patch<Bf16Traits, 2, 2>(rt, p, halo8, 128 + 2 * halo8) : launch_patch<F16Traits, 2, 2>(rt, p, halo8, 128 + 2 * halo8);
+    case kFormResident: return bf ? launch_resident<Bf16Traits>(rt, p, halo8) : launch_resident<F16Traits>(rt, p, halo8);
+    case kFormS1_1_4_32: return bf ? launch_s1<Bf16Traits, 1, 4, 32>(rt, p) : launch_s1<F16Traits, 1, 4, 32>(rt, p);
+    case kFormS1_2_2_32: return bf ? launch_s1<Bf16Traits, 2, 2, 32>(rt, p) : launch_s1<F16Traits, 2, 2, 32>(rt, p);
+    default: return bf ? launch_s1<Bf16Traits, 2, 2, 64>(rt, p) : launch_s1<F16Traits, 2, 2, 64>(rt, p);
+    }
+}
+
+// `plan`: conv_s1_plan of a conv_s1_shape problem. Returns -1 when the operands do not qualify (the caller takes its next candidate).
+int launch_conv_s1(infiniRocmRuntime_t rt, int dtype, const void *x, const void *w, const void *bias, const void *res, void *y,
+                   const ConvProblem &q, const ConvS1Plan &plan, const ConvHooks &hk) {
+    if (((uintptr_t)w & 15) != 0 || ((uintptr_t)x & 3) != 0)
+        return -1;
+    ConvS1Args p;
+    PhaseSplitArgs ps;
+    if (!fill_args(p, ps, x, w, bias, res, y, q, plan, hk))
+        return -1;
+    // workspace: [ packed weights (unless cached) | phase planes | the tap GEMM's split-K exchange slab (fp32 partial row blocks) ]
+    const bool rowtap = q.c % 32 != 0, split = q.sh * q.sw > 1;
+    const size_t w_bytes = rowtap ? (((size_t)p.f * p.kpad * 2 + 255) & ~(size_t)255)
+                                  : (q.r * q.s > 1 ? (((size_t)p.f * p.kdim * 2 + 255) & ~(size_t)255) : 0);
+    const bool cached = w_bytes && rt->conv_const_weights;
+    const size_t planes_off = cached ? 0 : w_bytes;
+    // (+256: the pixel-slot GEMM a strided pointwise layer continues with reads up to 14 bytes past a ragged last plane)
+    const size_t planes_end = planes_off + (split ? (size_t)p.x_bytes + 256 : 0);
+    const size_t slab_off = (planes_end + 255) & ~(size_t)255;
+    const size_t ws_bytes = plan.tap_slab_bytes ? slab_off + plan.tap_slab_bytes : planes_end;
+    char *ws = nullptr;
+    if (ws_bytes)
+        if (const int st = infini_rocm_workspace(rt, ws_bytes, (void **)&ws); st != INFINI_ROCM_OK)
+            return st;
+    if (w_bytes)
+        if (const int st = pack_weights(rt, w, p, rowtap, w_bytes, cached, ws, &p.w); st != INFINI_ROCM_OK)
+            return st;
+    if (split) {
+        if (const int st = split_phases(rt, p, ps, x, (unsigned short *)(ws + planes_off)); st != INFINI_ROCM_OK)
+            return st;
         p.x = ps.o;
         // a strided 1 x 1 layer (ResNet's down-sampling branches) reads ONE phase: the plane set just written is a dense
-        // [n][c][oh][ow] activation, i.e. a unit-stride pointwise layer — one GEMM over pixel slots on the persistent kernels
-        // when it has the filters to fill their 256-row tiles (conv.hip has the rule and the numbers)
-        if (r == 1 && s == 1 && ps.nslots == 1 && c % 64 == 0 && (act == 0 || act == 1) &&
-            (rt->conv_variant == 5 ||
-             (rt->conv_variant < 0 && f >= 128 && ceil_div(f, 256) * ceil_div((long)n * ((oh * ow + 7) / 8 * 8), 256) * 16 >= rt->num_cu * 3))) {
-            const int st = launch_conv_pw_gemm(rt, dtype, ps.o, w, bias, res, y, n, c, (long)oh * ow, f, act);
-            if (st >= 0)
+        // [n][c][oh][ow] activation, i.e. a unit-stride pointwise layer (conv_pixel_gemm_wanted has the rule and the numbers)
+        if (plan.pixel_gemm)
+            if (const int st = launch_conv_pw_gemm(rt, dtype, ps.o, w, bias, res, y, q.n, q.c, p.hw, q.f, q.act, hk); st >= 0)
                 return st;
-        }
     }
-    if (tap_want) {
-        bool safe = true;
-        if (!split) {
-            // a tap moves a 16-byte run by up to one row + one pixel: the bytes in front of and behind X it then reaches (masked away,
-            // but fetched) must be readable memory. True inside an arena of infini_rocm_alloc (256 bytes of slack on both sides) and
-            // for a tensor in the middle of a caller's block; a tensor at the very edge of its allocation takes the other kernels.
-            const long reach = ((long)ow + 1) * 2 + 16;
-            hipDeviceptr_t base = nullptr;
-            size_t size = 0;
-            if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)x) != hipSuccess) {
-                (void)hipGetLastError();
-                safe = false;
-            } else {
-                const char *lo = (const char *)x - reach, *hi = (const char *)x + p.plane_elems * 2 + reach;
-                safe = lo >= (const char *)base && hi <= (const char *)base + size;
-            }
-        }
-        if (safe) {
-            const int st = launch_conv_tap_gemm(rt, dtype, p.x, p.w, bias, y, n, c, oh, ow, h, wd, sh, p.plane_elems, f, act, tap_split,
-                                                tap_slab_bytes ? ws + ws_slab_off : nullptr, tap_slab_bytes);
-            if (st >= 0)
-                return st;
-        }
-        if (split && rt->conv_variant == 7) // (the tap-shifted kernel below reads the planes through p.slot: any order serves it)
-            rt->last_conv_route = "tap_shifted";
-    }
-    const bool bf = dtype == INFINI_DT_BF16;
-    static const int pw_on = getenv("IROCM_CONV_PW") ? atoi(getenv("IROCM_CONV_PW")) : 1; // tuning hook: 0 = off
-    if (pw_on && r == 1 && s == 1 && ph == 0 && pw == 0 && c % 64 == 0 && c <= (pw_on == 2 ? 256 : 128) && f > 64 && p.hw % 2 == 0)
-        return bf ? launch_pw<Bf16Traits>(rt, p) : launch_pw<F16Traits>(rt, p);
-    if (rowtap)
-        return bf ? launch_s1<Bf16Traits, 1, 4, 32, true>(rt, p) : launch_s1<F16Traits, 1, 4, 32, true>(rt, p);
-    // unit-stride "same" R x S (the 3x3 layers): input patch resident in LDS, every tap an aligned row offset
-    static const int patch_on = getenv("IROCM_CONV_PATCH") ? atoi(getenv("IROCM_CONV_PATCH")) : 1; // tuning hook: 0 = off
-    if (patch_on && r * s > 1 && r * s <= 32 && !split && dh == 1 && dw == 1 && oh == h && ow == wd && 2 * ph == r - 1 &&
-        2 * pw == s - 1 && c % 32 == 0 && rt->conv_variant != 4) { // variant 4: the tap-shifted kernel (A/B)
-        const int halo8 = (ph * wd + pw + 7) & ~7;
-        // 128 f x 128 slots. (The 64 f x 256 slots form of the same kernel, <1, 4>, was measured on ResNet's C64 -> F64
-        // 56x56 layers — two channel blocks, 18 taps per workgroup: 119 us against 96 us for the tap-shifted kernel, whose
-        // 64 x 256 x 32 tile has no patch / transpose prologue to amortise — and is not instantiated.)
-        // 128 f x 256 slots on 8 waves (one workgroup per CU, three weight stages) when that still fills most of the chip: every
-        // weight tile streamed from L2 then serves twice the slots. C128 28x28 60.6 -> 58.3 us, C256 14x14 55.1 -> 51.6; C512 7x7
-        // (100 workgroups) 73.8 -> 83.2: stays on the 4-wave form. IROCM_CONV_PATCH_WIDE = 0 / 1 forces either (A/B); conv variant 6 forces the wide form (tests, tune()).
-        static const int patch_wide = getenv("IROCM_CONV_PATCH_WIDE") ? atoi(getenv("IROCM_CONV_PATCH_WIDE")) : -1;
-        const bool wide_fills = ceil_div(f, 128) * ceil_div(p.ncols, 256) * 10 >= (long)rt->num_cu * 7;
-        if (f > 64 && 2 * halo8 <= 128 && (patch_wide == 1 || rt->conv_variant == 6 || (patch_wide < 0 && wide_fills)))
-            return bf ? launch_patch<Bf16Traits, 2, 4>(rt, p, halo8, 256 + 2 * halo8)
-                      : launch_patch<F16Traits, 2, 4>(rt, p, halo8, 256 + 2 * halo8);
-        if (f > 64 && 2 * halo8 <= 128)
-            return bf ? launch_patch<Bf16Traits, 2, 2>(rt, p, halo8, 128 + 2 * halo8)
-                      : launch_patch<F16Traits, 2, 2>(rt, p, halo8, 128 + 2 * halo8);
-        // F <= 64, C <= 64: the whole weight tensor resident in LDS, persistent workgroups over 256-slot tiles (conv_resident)
-        static const int resident_on = getenv("IROCM_CONV_RESIDENT") ? atoi(getenv("IROCM_CONV_RESIDENT")) : 1; // A/B hook
-        if (resident_on && f <= 64 && c <= 64 && p.hw % 8 == 0 && 2 * halo8 <= 128 && (((uintptr_t)x) & 15) == 0 && !res &&
-            r == 3 && s == 3 && ph == 1 && pw == 1 && (c == 32 || c == 64) && p.wide_epilogue == 2 && rt->conv_variant != 4)
-            return bf ? launch_resident<Bf16Traits>(rt, p, halo8) : launch_resident<F16Traits>(rt, p, halo8);
-    }
-    if (f <= 64)
-        return bf ? launch_s1<Bf16Traits, 1, 4, 32>(rt, p) : launch_s1<F16Traits, 1, 4, 32>(rt, p);
-    static const int cfg = getenv("IROCM_CONV_CFG") ? atoi(getenv("IROCM_CONV_CFG")) : 0; // tuning hook
-    if (c % 64 != 0 || cfg == 1)
-        return bf ? launch_s1<Bf16Traits, 2, 2, 32>(rt, p) : launch_s1<F16Traits, 2, 2, 32>(rt, p);
-    return bf ? launch_s1<Bf16Traits, 2, 2, 64>(rt, p) : launch_s1<F16Traits, 2, 2, 64>(rt, p);
+    if (plan.tap && (split || tap_reach_readable(x, p)))
+        if (const int st = launch_conv_tap_gemm(rt, dtype, p.x, p.w, bias, y, q.n, q.c, q.oh, q.ow, (int)q.h, (int)q.w, q.sh, p.plane_elems, q.f,
+                                                q.act, plan.tap_split, plan.tap_slab_bytes ? ws + slab_off : nullptr, plan.tap_slab_bytes, hk);
+            st >= 0)
+            return st;
+    // (the tap-shifted kernels read the planes through p.slot: the tap mode's fixed order serves them too)
+    const ConvForm form = (plan.form == kFormResident && (((uintptr_t)x) & 15) != 0) ? kFormS1_1_4_32 : plan.form;
+    return launch_form(rt, dtype == INFINI_DT_BF16, p, form, plan.halo8);
 }
 
 } // namespace irocm

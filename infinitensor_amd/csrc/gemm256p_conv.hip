@@ -1,6 +1,7 @@
 // gemm256p in conv mode (gemm256p_kernel.h, CONV): pointwise convolutions with >= 256 filters as ONE GEMM over pixel slots.
 // One translation unit for the three tile widths (A K-major, B gathered from NCHW: one layout each).
 #include "gemm256p_kernel.h"
+#include "conv_internal.h"
 
 namespace irocm {
 namespace g256p {
@@ -26,12 +27,10 @@ int launch_gemm256p_conv(infiniRocmRuntime_t rt, int dtype, const GemmArgs &p, i
 
 } // namespace g256p
 
-int persist_pick_nt(long m, long n, long k, int cus, int max_nt);
-
 // Pointwise convolution as one GEMM over pixel slots (see infini_rocm_conv2d_res). Returns -1 when the operands do not qualify
 // (the caller falls through to the other kernels), a status otherwise.
 int launch_conv_pw_gemm(infiniRocmRuntime_t rt, int dtype, const void *x, const void *w, const void *bias, const void *res,
-                               void *y, int64_t n, int64_t c, int64_t hw, int64_t f, int act) {
+                        void *y, int64_t n, int64_t c, int64_t hw, int64_t f, int act, const ConvHooks &hk) {
     const int64_t hwp = (hw + 7) & ~(int64_t)7;
     if (hw < 8 || (((uintptr_t)w) & 15) != 0 || (((uintptr_t)x) & 1) != 0 || (((uintptr_t)y) & 1) != 0)
         return -1;
@@ -65,8 +64,7 @@ int launch_conv_pw_gemm(infiniRocmRuntime_t rt, int dtype, const void *x, const 
     p.cv_res_bytes = (unsigned)(n * f * hw * 2); // (< 2^32: checked above)
     // the 256-column residual copy spills 36-48 bytes per lane (epilogue only) and still wins where the cost model picks it:
     // C256 -> F1024 @14x14 with a residual 40.4 vs 46.9 us on 192-column tiles, C512 -> F2048 @7x7 30.7 vs 36.6 (IROCM_CONV_RES_NT4=0: A/B)
-    static const int res_nt4 = getenv("IROCM_CONV_RES_NT4") ? atoi(getenv("IROCM_CONV_RES_NT4")) : 1;
-    int nt = persist_pick_nt(f, n * hwp, c, rt->num_cu, (res && !res_nt4) ? 3 : 4);
+    int nt = persist_pick_nt(f, n * hwp, c, rt->num_cu, (res && !hk.res_nt4) ? 3 : 4);
     // The cost model is fitted on MFMA-bound GEMMs, where a partial last round of tiles costs most of a full one. Layers with C <= 512
     // are HBM-bound (4-8 K-tiles per tile): a partial round simply has the bandwidth to itself, and narrower tiles only add tile
     // boundaries — measured at batch 128 (tools/gpu_r5k.sh, us with the model's width / 256 columns): C512 -> 128 @28^2 39.4 / 34.8,
@@ -75,12 +73,9 @@ int launch_conv_pw_gemm(infiniRocmRuntime_t rt, int dtype, const void *x, const 
     // half the residual registers in flight per wave, twice the tiles to balance (103.3 / 109.2).
     if (c <= 512)
         nt = (res && c <= 64) ? 2 : 4;
-    if (const char *force = getenv("IROCM_CONV_PW_NT")) { // test hook (read per call): force the tile width 2 / 3 / 4
-        const int v = atoi(force);
-        if (v >= 2 && v <= 4)
-            nt = v;
-    }
-    rt->last_conv_route = "pixel_gemm";
+    if (hk.pw_nt >= 2 && hk.pw_nt <= 4) // test hook: force the tile width
+        nt = hk.pw_nt;
+    rt->last_conv_route = conv_route_name(kRoutePixelGemm);
     return g256p::launch_gemm256p_conv(rt, dtype, p, nt);
 }
 

@@ -20,6 +20,7 @@
 // 0-31) and k = 4 + s (lanes 32-63) — any pairing is fine as long as both operands use the same one. The operands are
 // swapped (D = B^T-fragment x A-fragment) so that a lane ends up with 4 consecutive n of one m row: 16-byte stores.
 #include "gemm_common.h"
+#include "conv_internal.h"
 #include <type_traits>
 
 namespace irocm {
@@ -624,7 +625,7 @@ int launch_fast32(infiniRocmRuntime_t rt, GemmArgs p, bool bkm, int small) {
 // (the caller keeps conv_direct32), a status otherwise.
 int launch_conv_igemm32(infiniRocmRuntime_t rt, const void *x, const void *w, const void *bias, const void *res, void *y, int64_t n,
                         int64_t c, int64_t h, int64_t wd, int64_t f, int r, int s, int ph, int pw, int sh, int sw, int dh, int dw, int oh,
-                        int ow, int act) {
+                        int ow, int act, const ConvHooks &hk) {
     const int64_t ncols = n * oh * ow;
     const bool tm = c >= 32; // tap-major K over re-packed weights (see the kernel); layers with fewer channels decode k per element
     const int64_t cp = tm ? (c + 31) / 32 * 32 : c;
@@ -642,8 +643,8 @@ int launch_conv_igemm32(infiniRocmRuntime_t rt, const void *x, const void *w, co
     // 109 / 217: the 64^2 tiles (83 registers, 32 KB of LDS: five workgroups per CU hide the gather's latency) win everywhere there, so
     // the 128^2 form (182 registers, two workgroups per CU) is kept for problems with at least eight of its tiles per CU only.
     bool small = f <= 64 || ceil_div(f, 128) * ceil_div(ncols, 128) < 8 * (int64_t)rt->num_cu;
-    if (const char *e = getenv("IROCM_CONV32_TILE")) // measurement hook (tools/conv32_bench.py --forms): 1 = 64^2 tiles, 2 = 128^2
-        small = atoi(e) == 1 ? true : (atoi(e) == 2 ? false : small);
+    if (hk.conv32_tile == 1 || hk.conv32_tile == 2) // measurement hook (tools/conv32_bench.py --forms): 1 = 64^2 tiles, 2 = 128^2
+        small = hk.conv32_tile == 1;
     const int bm = small ? 64 : 128;
     const int64_t tiles = ceil_div(f, bm) * ceil_div(ncols, bm);
     // Split-K: the 64^2 tiles of a 7 x 7-plane layer at batch 32 number 200 (one per CU, no partner to hide the gather behind) with
@@ -656,9 +657,9 @@ int launch_conv_igemm32(infiniRocmRuntime_t rt, const void *x, const void *w, co
     int split = 1;
     if (small && ((tiles <= rt->num_cu && nk_all >= 32) || (tiles <= 2 * (int64_t)rt->num_cu && nk_all >= 64)))
         split = 4;
-    if (const char *e = getenv("IROCM_CONV32_SPLIT")) // measurement / test hook: 1 = never, 2 / 4 = that factor wherever a slice keeps >= 2 K-tiles
-        if (small && atoi(e) >= 1 && atoi(e) <= 8 && nk_all >= 2 * atoi(e))
-            split = atoi(e);
+    // measurement / test hook: 1 = never, 2 / 4 = that factor wherever a slice keeps >= 2 K-tiles
+    if (small && hk.conv32_split >= 1 && hk.conv32_split <= 8 && nk_all >= 2 * hk.conv32_split)
+        split = hk.conv32_split;
     const int64_t out_elems = n * f * oh * ow;
     const size_t partial_bytes = split > 1 ? (size_t)split * out_elems * 4 : 0;
     float *partial = nullptr;
@@ -772,7 +773,7 @@ int launch_conv_igemm32(infiniRocmRuntime_t rt, const void *x, const void *w, co
 #undef IROCM_C32
     IROCM_LAUNCH_CHECK("conv_igemm32");
     if (split > 1) {
-        rt->last_conv_route = "igemm32_splitk";
+        rt->last_conv_route = conv_route_name(kRouteIgemm32SplitK);
         const int ohw = oh * ow;
         const bool v4 = ohw % 4 == 0 && ((((uintptr_t)y) | ((uintptr_t)partial) | (res ? (uintptr_t)res : 0)) & 15) == 0;
         long g = ceil_div(out_elems / (v4 ? 4 : 1), 256);

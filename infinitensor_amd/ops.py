@@ -190,9 +190,22 @@ def weight_cache_info(rt: RocmRuntime) -> dict:
     return {"entries": n.value, "bytes": b.value, "epoch": e.value}
 
 
+def conv_plan_route(dtype: torch.dtype, n: int, c: int, h: int, w: int, f: int, r: int, s: int, ph: int, pw: int, sh: int = 1, sw: int = 1,
+                    dh: int = 1, dw: int = 1, groups: int = 1, act: int = 0, residual: bool = False, variant: int = -1,
+                    num_cu: int = 256) -> tuple[str, str]:
+    """(route, kernel form) conv2d would launch first for this problem (infini_rocm_conv2d_plan_route: pure, no GPU)."""
+    import ctypes as C
+
+    route, form = C.c_char_p(), C.c_char_p()
+    check(lib().infini_rocm_conv2d_plan_route(int(_TORCH2DT[dtype]), n, c, h, w, f, r, s, ph, pw, sh, sw, dh, dw, groups, act, int(residual),
+                                              int(variant), int(num_cu), C.byref(route), C.byref(form)))
+    return route.value.decode(), form.value.decode()
+
+
 def set_conv_variant(rt: RocmRuntime, variant: int) -> None:
     """-1 heuristic, 1 generic implicit GEMM, 2 conv_s1 wherever eligible, 3 batched-GEMM route for pointwise, 4 = 2 without the patch
-    kernel, 5 pointwise layers as one pixel-slot GEMM, 6 = 2 with the 8-wave patch kernel (include/infini_rocm.h)."""
+    kernel, 5 pointwise layers as one pixel-slot GEMM, 6 = 2 with the 8-wave patch kernel, 7 3 x 3 layers as one tap GEMM (include/infini_rocm.h;
+    enum ConvVariant in csrc/conv_route.h)."""
     check(lib().infini_rocm_conv2d_set_variant(rt.handle, int(variant)))
 
 
