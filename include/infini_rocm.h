@@ -228,6 +228,14 @@ const char *infini_rocm_matmul_variant_name(int variant);
  * the forced setting resolved to for that shape. Measurement tools stamp their records with it (bench.py refuses counter
  * files taken from another kernel). */
 int infini_rocm_matmul_last_variant(infiniRocmRuntime_t rt, int *variant);
+/* What infini_rocm_matmul_grouped would launch, without a runtime or a GPU (csrc/gemm_route.h: gemm_plan): *name = the variant's name,
+ * *splits = the split-K factor (1 unless the answer is tile256_splitk; "none" / 0 for an empty problem). Same argument checks as the
+ * launch. has_bias: a bias is given; compute_type / variant: what infini_rocm_matmul_set_compute_type / _set_variant would hold;
+ * num_cu: the device's CU count; a_lo / b_lo / c_lo: the low four address bits of the operands (0 = 16-byte aligned). */
+int infini_rocm_matmul_plan_route(int dtype, int64_t batch, int64_t m, int64_t n, int64_t k, int trans_a, int trans_b, int64_t stride_a,
+                                  int64_t stride_b, int64_t stride_c, int has_bias, int64_t bias_stride_m, int64_t bias_stride_n, int act,
+                                  int64_t head_dim, int compute_type, int variant, int num_cu, int a_lo, int b_lo, int c_lo,
+                                  const char **name, int *splits);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Softmax along one axis (reference: softmax_kernel, src/kernels/cuda/softmax.cu:242-404;      */

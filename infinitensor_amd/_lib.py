@@ -93,6 +93,8 @@ def lib() -> C.CDLL:
     sig("infini_rocm_matmul_set_variant", [vp, i32])
     sig("infini_rocm_matmul_last_variant", [vp, C.POINTER(C.c_int)])
     sig("infini_rocm_matmul_may_use_workspace", [vp, i64, i64, i64, C.POINTER(C.c_int)])
+    sig("infini_rocm_matmul_plan_route", [i32, i64, i64, i64, i64, i32, i32, i64, i64, i64, i32, i64, i64, i32, i64, i32, i32, i32, i32, i32, i32,
+                                          C.POINTER(C.c_char_p), C.POINTER(C.c_int)])
     sig("infini_rocm_matmul_num_variants", [], i32)
     sig("infini_rocm_matmul_variant_name", [i32], C.c_char_p)
     sig("infini_rocm_softmax", [vp, i32, vp, vp, i64, i64, i64])

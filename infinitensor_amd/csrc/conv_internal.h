@@ -27,7 +27,4 @@ int launch_conv_tap_gemm(infiniRocmRuntime_t rt, int dtype, const void *x, const
                          int64_t c, int oh, int ow, int in_h, int in_w, int stride, int64_t plane_elems, int64_t f, int act,
                          int split, void *slab, size_t slab_bytes, const ConvHooks &hk);
 
-// gemm.hip: tile width (2 / 3 / 4 x 64 columns) of the persistent 256-row kernels by the cost model
-int persist_pick_nt(long m, long n, long k, int cus, int max_nt);
-
 } // namespace irocm

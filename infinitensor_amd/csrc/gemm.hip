@@ -21,7 +21,6 @@
 //   gemm256p (gemm256p_kernel.h)   : the same inner loop as ONE persistent workgroup per CU walking its tiles through a
 //       flat K-tile pipeline (no cold prologue after the first tile, epilogues overlapped); tile widths 256 / 192 / 128.
 #include "gemm_common.h"
-#include <type_traits>
 
 namespace irocm {
 
@@ -408,7 +407,6 @@ __global__ __launch_bounds__(256) void gemm_fast128(GemmArgs p) {
 
 // implemented in gemm256.hip
 int launch_gemm256(infiniRocmRuntime_t rt, int dtype, const GemmArgs &p, bool a_kmajor, bool b_kmajor);
-bool gemm256_supported(const GemmArgs &p, bool a_kmajor, bool b_kmajor);
 namespace g256p { // persistent multi-tile kernels, tile 256 x 64 NT (gemm256p_kernel.h)
 int launch_gemm256p_nt4(infiniRocmRuntime_t rt, int dtype, const GemmArgs &p, bool akm, bool bkm);
 int launch_gemm256p_nt3(infiniRocmRuntime_t rt, int dtype, const GemmArgs &p, bool akm, bool bkm);
@@ -418,11 +416,9 @@ int launch_gemm256p_trace(infiniRocmRuntime_t rt, int dtype, const GemmArgs &p, 
 int launch_gemm256_splitk(infiniRocmRuntime_t rt, int dtype, const GemmArgs &p, bool a_kmajor, bool b_kmajor, int splits);
 int launch_gemm256_f32out(infiniRocmRuntime_t rt, int dtype16, const GemmArgs &p, bool a_kmajor, bool b_kmajor, int splits, float *planes);
 namespace g128w { // four waves x 128 x 128 wave tiles, four-stage ring (gemm128w.hip): plain GEMMs on whole 256^2 tiles, K % 128 == 0
-bool supported(const GemmArgs &p);
 int launch_gemm128w(infiniRocmRuntime_t rt, int dtype, const GemmArgs &p, bool akm, bool bkm);
 } // namespace g128w
 // implemented in gemm32.hip: the fp32 128^2 LDS-DMA tile kernel (v_mfma_f32_32x32x2_f32)
-bool fast32_supported(const GemmArgs &p, bool a_kmajor, bool b_kmajor);
 int launch_fast32(infiniRocmRuntime_t rt, GemmArgs p, bool b_kmajor, int small_tiles);
 
 template <typename Tr> static int launch_fast128(infiniRocmRuntime_t rt, GemmArgs p, bool akm, bool bkm) {
@@ -430,83 +426,52 @@ template <typename Tr> static int launch_fast128(infiniRocmRuntime_t rt, GemmArg
     p.tiles_n = (int)ceil_div(p.n, f128::BN);
     const unsigned grid = (unsigned)p.tiles_m * p.tiles_n * p.batch;
     const size_t lds = 4 * f128::TILE_BYTES;
-#define IROCM_F128(AK, BK_)                                                                        \
-    do {                                                                                           \
-        auto kern = gemm_fast128<Tr, AK, BK_>;                                                     \
-        IROCM_LDS_ATTR(kern, (int)lds, rt);                                                        \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, rt->stream, p);                       \
-    } while (0)
-    if (akm && bkm) IROCM_F128(true, true);
-    else if (akm && !bkm) IROCM_F128(true, false);
-    else if (!akm && bkm) IROCM_F128(false, true);
-    else IROCM_F128(false, false);
-#undef IROCM_F128
-    IROCM_LAUNCH_CHECK("gemm_fast128");
+    return with_layout(akm, bkm, [&](auto ak, auto bk) -> int {
+        auto kern = gemm_fast128<Tr, decltype(ak)::value, decltype(bk)::value>;
+        IROCM_LDS_ATTR(kern, (int)lds, rt);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, rt->stream, p);
+        IROCM_LAUNCH_CHECK("gemm_fast128");
+        return INFINI_ROCM_OK;
+    });
+}
+
+static int launch_generic64(infiniRocmRuntime_t rt, int dtype, GemmArgs p) {
+    p.tiles_m = (int)ceil_div(p.m, 64);
+    p.tiles_n = (int)ceil_div(p.n, 64);
+    IROCM_CHECK_ARG((int64_t)p.tiles_m * p.tiles_n < (1ll << 31), "matmul: too many tiles");
+    dim3 grid((unsigned)(p.tiles_m * p.tiles_n), 1, (unsigned)p.batch);
+    if (dtype == INFINI_DT_F32)
+        hipLaunchKernelGGL(gemm_generic32, grid, dim3(256), 0, rt->stream, p);
+    else if (dtype == INFINI_DT_BF16)
+        hipLaunchKernelGGL(gemm_generic16<Bf16Traits>, grid, dim3(256), 0, rt->stream, p);
+    else
+        hipLaunchKernelGGL(gemm_generic16<F16Traits>, grid, dim3(256), 0, rt->stream, p);
+    IROCM_LAUNCH_CHECK("gemm_generic");
     return INFINI_ROCM_OK;
 }
 
-static bool aligned16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
-
-static bool fast128_supported(const GemmArgs &p, bool akm, bool bkm) {
-    if (p.k % 8 != 0 || p.k < 8) // 16-byte K runs; a K tail inside the last 64-wide tile is zero-filled
-        return false;
-    if (!aligned16(p.a) || !aligned16(p.b) || (p.a_bs % 8) || (p.b_bs % 8))
-        return false;
-    if (!akm && (p.m % 8 != 0 || p.m < 8))
-        return false;
-    if (!bkm && (p.n % 8 != 0 || p.n < 8))
-        return false;
-    if (!aligned16(p.c) && (p.n % 4 == 0))
-        return false;
-    return true;
-}
-
-// gemm128w.hip keeps a lane's byte offset from the tile corner — the rows of its pieces PLUS the whole k advance of a tile — in 32 bits
-static bool w128_offsets_fit(const GemmArgs &p, bool akm, bool bkm) {
-    const long lda = akm ? p.a_rs : p.a_cs, ldb = bkm ? p.b_cs : p.b_rs;
-    const long a_max = akm ? (255 * lda + p.k + 64) * 2 : ((long)(p.k + 32) * lda + 256) * 2;
-    const long b_max = bkm ? (255 * ldb + p.k + 64) * 2 : ((long)(p.k + 32) * ldb + 256) * 2;
-    return a_max < (1ll << 32) && b_max < (1ll << 32);
-}
-
-static const char *kVariantNames[] = {"generic64", "fast128_glds", "tile256", "tile256_splitk", "persist256", "persist192",
-                                      "persist128", "fast32", "wave128"};
-constexpr int kNumVariants = 9; // 1-6 and 8 serve f16 / bf16, 7 serves f32, 0 everything
-
-// Cost model behind the heuristic (microseconds; fitted to tools/gemm_shapes.py on MI355X, bf16 / f16, N(0,1) data).
-// A workgroup of the persistent kernel walks its tiles: a K-tile of a 256 x 64 NT tile costs kKt[NT]; every tile pays its
-// tile boundary (both wave rows' epilogues side by side + the pipeline restart; gemm256p_kernel.h); launch + first prologue
-// ~3 us once. Re-fitted after the epilogues were de-serialised (round 2: ~12.4 k cycles per boundary) and again after their
-// stores went quad-contiguous (round 3: ~7.9 k cycles; profiles/r03_gemm_shapes_bf16.txt).
-static const double kKt[5] = {0, 0, 0.91, 1.10, 1.40};
-static const double kStoreTail[5] = {0, 0, 4.2, 5.2, 5.5};
-static double persist_cost(long m, long n, long k, long batch, int nt, int cus) {
-    const long tiles = ceil_div(m, 256) * ceil_div(n, 64 * nt) * batch;
-    const long full = tiles / cus;
-    const double frac = (double)(tiles - full * cus) / cus;
-    // a partial last round still costs most of a tile time (every workgroup's tile takes what it takes; only the shared
-    // L2 / HBM / power budget is lighter): 0.55 + 0.5 frac of a full round fits the sweep from frac = 0.25 to 0.8
-    const double waves = (double)full + (frac > 0 ? (0.55 + 0.5 * frac < 1.0 ? 0.55 + 0.5 * frac : 1.0) : 0.0);
-    return waves * ((double)(k / 64) * kKt[nt] + kStoreTail[nt]) + 3.0;
-}
-// split-K: `splits` workgroups per 256^2 tile write fp32 partial planes, one reduce pass adds them
-static double splitk_cost(long m, long n, long k, long batch, int splits) {
-    return 3.0 + (double)(k / 64) / splits * kKt[4] + 12.0 + (double)batch * m * n * (4.0 * splits + 2.0) / 5.0e6;
-}
-
-// tile width (NT = 4 / 3 / 2 -> 256 / 192 / 128 columns) the cost model prefers for an m x n x k problem on the persistent
-// kernels; max_nt caps it (the conv mode's residual copy exists up to NT = 3)
-int persist_pick_nt(long m, long n, long k, int cus, int max_nt) {
-    int best_nt = max_nt < 4 ? max_nt : 4;
-    double best = 1e30;
-    for (int nt = best_nt; nt >= 2; --nt) {
-        const double c = persist_cost(m, n, k, 1, nt, cus);
-        if (c < best * 0.97) {
-            best = c;
-            best_nt = nt;
-        }
-    }
-    return best_nt;
+// The reduced-precision compute types of an fp32 MatMul (gemm_reduced_precision_ok): A and B are cast once into the workspace —
+// (stride ? batch : 1) dense blocks each — and the split-K kernel writes fp32. The plan was made on shape and alignment alone, so
+// the workspace is grown only for a problem that takes this path.
+static int launch_f32_reduced(infiniRocmRuntime_t rt, int compute_type, GemmArgs p, bool akm, bool bkm, int splits) {
+    const int dt16 = compute_type == 1 ? INFINI_DT_BF16 : INFINI_DT_F16;
+    const int64_t mk = (int64_t)p.m * p.k, nk = (int64_t)p.n * p.k, mn = (int64_t)p.m * p.n;
+    const bool a_shared = p.a_bs == 0 || p.batch == 1, b_shared = p.b_bs == 0 || p.batch == 1;
+    const int64_t na = (a_shared ? 1 : p.batch) * mk, nb = (b_shared ? 1 : p.batch) * nk;
+    const size_t a_bytes = ((size_t)na * 2 + 255) & ~(size_t)255, b_bytes = ((size_t)nb * 2 + 255) & ~(size_t)255;
+    char *ws = nullptr;
+    int st = infini_rocm_workspace(rt, a_bytes + b_bytes + (size_t)splits * p.batch * mn * sizeof(float), (void **)&ws);
+    if (st == INFINI_ROCM_OK)
+        st = infini_rocm_cast(rt, INFINI_DT_F32, dt16, p.a, ws, na);
+    if (st == INFINI_ROCM_OK)
+        st = infini_rocm_cast(rt, INFINI_DT_F32, dt16, p.b, ws + a_bytes, nb);
+    if (st != INFINI_ROCM_OK)
+        return st;
+    p.a = ws;
+    p.b = ws + a_bytes;
+    p.a_bs = a_shared ? 0 : mk;
+    p.b_bs = b_shared ? 0 : nk;
+    return launch_gemm256_f32out(rt, dt16, p, akm, bkm, splits, (float *)(ws + a_bytes + b_bytes));
 }
 
 } // namespace irocm
@@ -517,9 +482,7 @@ extern "C" {
 
 int infini_rocm_matmul_num_variants(void) { return kNumVariants; }
 
-const char *infini_rocm_matmul_variant_name(int v) {
-    return (v >= 0 && v < kNumVariants) ? kVariantNames[v] : "invalid";
-}
+const char *infini_rocm_matmul_variant_name(int v) { return matmul_variant_name(v); }
 
 int infini_rocm_matmul_last_variant(infiniRocmRuntime_t rt, int *variant) {
     IROCM_CHECK_ARG(rt && variant, "NULL argument");
@@ -546,15 +509,11 @@ int infini_rocm_matmul_set_variant(infiniRocmRuntime_t rt, int variant) {
     return INFINI_ROCM_OK;
 }
 
-// split-K (the only MatMul path that takes the runtime workspace: fp32 partial planes) needs few enough 256^2 tiles
-static bool splitk_possible(infiniRocmRuntime_t rt, int64_t m, int64_t n, int64_t batch) {
-    const long tiles256 = ceil_div(m, 256) * ceil_div(n, 256) * batch;
-    return tiles256 * 2 <= rt->num_cu + rt->num_cu / 4;
-}
-
+// Split-K's fp32 partial planes take the runtime workspace. (So do the 16-bit copies of the reduced-precision compute types, which
+// this answer does not know about: kept as it is — callers rely on today's answer, and changing it is a change of behaviour.)
 int infini_rocm_matmul_may_use_workspace(infiniRocmRuntime_t rt, int64_t batch, int64_t m, int64_t n, int *may) {
     IROCM_CHECK_ARG(rt && may, "NULL argument");
-    *may = (rt->matmul_variant == 3 || splitk_possible(rt, m, n, batch)) ? 1 : 0;
+    *may = (rt->matmul_variant == kGemmTile256SplitK || gemm_splitk_tiles_fit(batch, m, n, rt->num_cu)) ? 1 : 0;
     return INFINI_ROCM_OK;
 }
 
@@ -576,12 +535,8 @@ int infini_rocm_matmul_headsplit(infiniRocmRuntime_t rt, int dtype, const void *
                                       bias_stride_b, bias_stride_m, bias_stride_n, act, seq, head_dim);
 }
 
-int infini_rocm_matmul_grouped(infiniRocmRuntime_t rt, int dtype, const void *a, const void *b,
-                               const void *bias, void *c, int64_t batch, int64_t m, int64_t n, int64_t k,
-                               int trans_a, int trans_b, int64_t stride_a, int64_t stride_b, int64_t stride_c,
-                               int64_t bias_stride_b, int64_t bias_stride_m, int64_t bias_stride_n,
-                               int act, int64_t seq, int64_t head_dim) {
-    IROCM_CHECK_ARG(rt, "NULL runtime");
+// argument checks shared by the launch entry and infini_rocm_matmul_plan_route
+static int matmul_check_args(int dtype, int64_t batch, int64_t m, int64_t n, int64_t k, int64_t stride_c, int act, int64_t seq, int64_t head_dim) {
     IROCM_CHECK_ARG(stride_c == 0 || stride_c >= m * n || stride_c <= -(m * n) || batch <= 1,
                     "matmul: output blocks of %lld elements overlap at a batch stride of %lld", (long long)(m * n), (long long)stride_c);
     IROCM_CHECK_ARG(stride_c % 8 == 0, "matmul: the output batch stride must be a multiple of 8 elements (16-byte stores)");
@@ -598,12 +553,15 @@ int infini_rocm_matmul_grouped(infiniRocmRuntime_t rt, int dtype, const void *a,
     IROCM_CHECK_ARG(batch < 65536 && m < (1ll << 31) && n < (1ll << 31) && k < (1ll << 31),
                     "matmul: dimension too large");
     IROCM_CHECK_ARG(act >= 0 && act <= 5, "matmul: bad act %d", act);
-    if (batch == 0 || m == 0 || n == 0)
-        return INFINI_ROCM_OK;
-    IROCM_CHECK_ARG(a && b && c, "matmul: NULL operand");
+    return INFINI_ROCM_OK;
+}
 
+// everything of GemmArgs but the pointers
+static GemmArgs matmul_args(int64_t batch, int64_t m, int64_t n, int64_t k, int trans_a, int trans_b, int64_t stride_a, int64_t stride_b,
+                            int64_t stride_c, int64_t bias_stride_b, int64_t bias_stride_m, int64_t bias_stride_n, int act, int64_t seq,
+                            int64_t head_dim) {
     GemmArgs p;
-    p.a = a; p.b = b; p.bias = bias; p.c = c;
+    p.a = p.b = p.bias = p.zeros = nullptr; p.c = nullptr;
     p.m = (int)m; p.n = (int)n; p.k = (int)k; p.batch = (int)batch;
     p.a_rs = trans_a ? 1 : k; p.a_cs = trans_a ? m : 1; p.a_bs = stride_a;
     p.b_rs = trans_b ? 1 : n; p.b_cs = trans_b ? k : 1; p.b_bs = stride_b;
@@ -613,139 +571,79 @@ int infini_rocm_matmul_grouped(infiniRocmRuntime_t rt, int dtype, const void *a,
     p.tiles_m = p.tiles_n = 0;
     p.splitk = 1;
     p.partial = nullptr;
-    p.zeros = rt->zeros;
     p.epi16 = 1; // 16-byte epilogue stores
     p.hs_s = (int)seq;
     p.hs_d = (int)head_dim;
+    return p;
+}
+
+int infini_rocm_matmul_grouped(infiniRocmRuntime_t rt, int dtype, const void *a, const void *b,
+                               const void *bias, void *c, int64_t batch, int64_t m, int64_t n, int64_t k,
+                               int trans_a, int trans_b, int64_t stride_a, int64_t stride_b, int64_t stride_c,
+                               int64_t bias_stride_b, int64_t bias_stride_m, int64_t bias_stride_n,
+                               int act, int64_t seq, int64_t head_dim) {
+    IROCM_CHECK_ARG(rt, "NULL runtime");
+    if (const int st = matmul_check_args(dtype, batch, m, n, k, stride_c, act, seq, head_dim); st != INFINI_ROCM_OK)
+        return st;
+    if (batch == 0 || m == 0 || n == 0)
+        return INFINI_ROCM_OK;
+    IROCM_CHECK_ARG(a && b && c, "matmul: NULL operand");
+
+    GemmArgs p = matmul_args(batch, m, n, k, trans_a, trans_b, stride_a, stride_b, stride_c, bias_stride_b, bias_stride_m, bias_stride_n,
+                             act, seq, head_dim);
+    p.a = a; p.b = b; p.bias = bias; p.c = c;
+    p.zeros = rt->zeros;
     const bool akm = !trans_a, bkm = trans_b != 0;
 
-    // (batch strides: the casts below copy (stride ? batch : 1) CONTIGUOUS blocks of m * k (n * k) elements, so the path is taken only
-    // for operands that ARE such blocks — stride 0 (shared) or exactly one block; any other stride keeps the exact kernels.
-    // Round-4 advisor: with another stride the cast read the wrong rows and the kernel indexed the 16-bit copy past its end.)
-    const bool ct_strides = (stride_a == 0 || stride_a == m * k || batch == 1) && (stride_b == 0 || stride_b == n * k || batch == 1);
-    if (dtype == INFINI_DT_F32 && rt->matmul_compute_type != 0 && head_dim == 0 && stride_c == 0 && ct_strides) {
-        // reduced-precision products on request: 16-bit copies of A and B in the workspace, the 256^2 split-K kernel (raw fp32
-        // slice sums), fp32 output. Shapes it cannot serve (K % 64, alignment) keep the exact kernels: never LESS accurate than asked.
-        const int dt16 = rt->matmul_compute_type == 1 ? INFINI_DT_BF16 : INFINI_DT_F16;
-        const bool a_shared = stride_a == 0 || batch == 1, b_shared = stride_b == 0 || batch == 1;
-        const int64_t na = (a_shared ? 1 : batch) * m * k, nb = (b_shared ? 1 : batch) * n * k;
-        GemmArgs q = p;
-        q.a_bs = a_shared ? 0 : m * k;
-        q.b_bs = b_shared ? 0 : n * k;
-        const size_t a_bytes = ((size_t)na * 2 + 255) & ~(size_t)255, b_bytes = ((size_t)nb * 2 + 255) & ~(size_t)255;
-        // the support test reads alignment and shape only: a 256-byte-aligned stand-in for the workspace pointers decides it BEFORE
-        // the workspace is grown (an unsupported shape must not cost an allocation)
-        q.a = (const void *)(uintptr_t)256;
-        q.b = (const void *)(uintptr_t)(256 + a_bytes);
-        if (gemm256_supported(q, akm, bkm) && (((uintptr_t)c) & 15) == 0) {
-            const long tiles = ceil_div(m, 256) * ceil_div(n, 256) * batch;
-            int splits = (int)std::max<long>(1, rt->num_cu / tiles);
-            splits = std::min(splits, std::max(1, (int)(k / 512)));
-            splits = std::min(splits, 16);
-            const size_t plane_bytes = (size_t)splits * batch * m * n * sizeof(float);
-            char *ws = nullptr;
-            int st = infini_rocm_workspace(rt, a_bytes + b_bytes + plane_bytes, (void **)&ws);
-            if (st != INFINI_ROCM_OK)
-                return st;
-            q.a = ws;
-            q.b = ws + a_bytes;
-            st = infini_rocm_cast(rt, INFINI_DT_F32, dt16, a, ws, na);
-            if (st == INFINI_ROCM_OK)
-                st = infini_rocm_cast(rt, INFINI_DT_F32, dt16, b, ws + a_bytes, nb);
-            if (st != INFINI_ROCM_OK)
-                return st;
-            rt->last_matmul_variant = 3;
-            return launch_gemm256_f32out(rt, dt16, q, akm, bkm, splits, (float *)(ws + a_bytes + b_bytes));
-        }
-    }
-    int variant = rt->matmul_variant;
-    if (dtype == INFINI_DT_F32) {
-        // fp32: the LDS-DMA tile kernel (gemm32.hip; 128^2 or 64^2 tiles) when it can serve the operands and the problem has
-        // at least 16 tiles of 64^2 (or it is forced); the generic register-staged 64^2 kernel otherwise
-        const long tiles64 = ceil_div(m, 64) * ceil_div(n, 64) * batch;
-        const bool want = variant == 7 || (variant < 0 && tiles64 >= 16 && k >= 64);
-        variant = (want && fast32_supported(p, akm, bkm)) ? 7 : 0;
-    } else if (variant == 7) {
-        variant = -1;
-    } else if (variant == 8 && !(g128w::supported(p) && w128_offsets_fit(p, akm, bkm))) {
-        variant = -1;
-    }
-    // split-K factor for the 256^2 kernel: fill the CUs when the tiles alone cannot and K is long enough that every
-    // slice still runs >= 8 K-tiles (the fp32 partial planes cost 8 bytes per output element and slice)
-    const long tiles256 = ceil_div(m, 256) * ceil_div(n, 256) * batch;
-    int splits = 1;
-    if (gemm256_supported(p, akm, bkm) && splitk_possible(rt, m, n, batch)) {
-        splits = (int)(rt->num_cu / tiles256);
-        const int max_by_k = (int)(k / (8 * 64));
-        if (splits > max_by_k) splits = max_by_k;
-        if (splits > 16) splits = 16;
-    }
-    if (variant < 0) {
-        // heuristic: the cheapest of {persistent 256 / 192 / 128-wide tiles, split-K} by the cost model when the 256-row
-        // kernels can serve the problem and it has at least ~half a tile per CU; otherwise 128^2 tiles; otherwise generic
-        const bool ok256 = gemm256_supported(p, akm, bkm);
-        double best = 1e30;
-        if (ok256) {
-            for (int nt = 4; nt >= 2; --nt) {
-                const long tiles = ceil_div(m, 256) * ceil_div(n, 64 * nt) * batch;
-                if (tiles * 2 < rt->num_cu)
-                    continue;
-                const double c = persist_cost(m, n, k, batch, nt, rt->num_cu);
-                if (c < best * 0.97) { // prefer the wider tile unless a narrower one is clearly cheaper
-                    best = c;
-                    variant = 4 + (4 - nt);
-                }
-            }
-            if (splits >= 2 && splitk_cost(m, n, k, batch, splits) < best * 0.97)
-                variant = 3;
-        }
-        // the four-wave kernel (gemm128w.hip) where it measured ahead of persist256 (profiles/r06_gemm_wave128_ab.txt: + 2-8 %): plain
-        // single-batch GEMMs of one or two rounds of whole 256^2 tiles with a long K, any layout but NT (both operands K-major: - 3.5 %)
-        if (variant == 4 && batch == 1 && k >= 2048 && !(akm && bkm) && tiles256 >= rt->num_cu && tiles256 <= 2l * rt->num_cu &&
-            g128w::supported(p) && w128_offsets_fit(p, akm, bkm))
-            variant = 8;
-        if (variant < 0)
-            variant = fast128_supported(p, akm, bkm) ? 1 : 0;
-    } else if (dtype == INFINI_DT_F32) {
-        // 0 or 7, decided above: the 16-bit kernels below never see fp32 operands
-    } else if (variant >= 2 && !gemm256_supported(p, akm, bkm)) {
-        variant = fast128_supported(p, akm, bkm) ? 1 : 0;
-    } else if (variant == 1 && !fast128_supported(p, akm, bkm)) {
-        variant = 0;
-    }
-
-    // sigmoid / tanh / erff-Gelu epilogues and biases other than one row vector live in the one-shot kernel (gemm256p_kernel.h)
-    if (variant >= 4 && variant <= 6 && (!(act == 0 || act == 1 || act == 5) || (p.bias && !(p.bias_m == 0 && p.bias_n == 1))))
-        variant = 2;
-    rt->last_matmul_variant = variant;
-    if (variant == 7) // 128^2 tiles when they give at least ~half a tile per CU, 64^2 tiles otherwise (512^3: 64 tiles)
-        return launch_fast32(rt, p, bkm, ceil_div(m, 128) * ceil_div(n, 128) * batch * 2 < rt->num_cu ? 1 : 0);
-    if (variant == 8)
+    const GemmPlan plan = gemm_plan(gemm_problem(p, dtype, akm, bkm, stride_c != 0), rt->matmul_variant, rt->matmul_compute_type, rt->num_cu);
+    rt->last_matmul_variant = plan.variant;
+    switch (plan.variant) {
+    case kGemmFast32:
+        return launch_fast32(rt, p, bkm, plan.fast32_small ? 1 : 0);
+    case kGemmWave128:
         return g128w::launch_gemm128w(rt, dtype, p, akm, bkm);
-    if (variant == 4)
+    case kGemmPersist256:
         return g256p::launch_gemm256p_nt4(rt, dtype, p, akm, bkm);
-    if (variant == 5)
+    case kGemmPersist192:
         return g256p::launch_gemm256p_nt3(rt, dtype, p, akm, bkm);
-    if (variant == 6)
+    case kGemmPersist128:
         return g256p::launch_gemm256p_nt2(rt, dtype, p, akm, bkm);
-    if (variant == 3)
-        return launch_gemm256_splitk(rt, dtype, p, akm, bkm, splits < 2 ? 2 : splits);
-    if (variant == 2)
+    case kGemmTile256SplitK:
+        return plan.reduced_precision ? launch_f32_reduced(rt, rt->matmul_compute_type, p, akm, bkm, plan.splits)
+                                      : launch_gemm256_splitk(rt, dtype, p, akm, bkm, plan.splits);
+    case kGemmTile256:
         return launch_gemm256(rt, dtype, p, akm, bkm);
-    if (variant == 1)
-        return dtype == INFINI_DT_BF16 ? launch_fast128<Bf16Traits>(rt, p, akm, bkm)
-                                       : launch_fast128<F16Traits>(rt, p, akm, bkm);
-    p.tiles_m = (int)ceil_div(m, 64);
-    p.tiles_n = (int)ceil_div(n, 64);
-    IROCM_CHECK_ARG((int64_t)p.tiles_m * p.tiles_n < (1ll << 31), "matmul: too many tiles");
-    dim3 grid((unsigned)(p.tiles_m * p.tiles_n), 1, (unsigned)batch);
-    if (dtype == INFINI_DT_F32)
-        hipLaunchKernelGGL(gemm_generic32, grid, dim3(256), 0, rt->stream, p);
-    else if (dtype == INFINI_DT_BF16)
-        hipLaunchKernelGGL(gemm_generic16<Bf16Traits>, grid, dim3(256), 0, rt->stream, p);
-    else
-        hipLaunchKernelGGL(gemm_generic16<F16Traits>, grid, dim3(256), 0, rt->stream, p);
-    IROCM_LAUNCH_CHECK("gemm_generic");
+    case kGemmFast128:
+        return dtype == INFINI_DT_BF16 ? launch_fast128<Bf16Traits>(rt, p, akm, bkm) : launch_fast128<F16Traits>(rt, p, akm, bkm);
+    default:
+        return launch_generic64(rt, dtype, p);
+    }
+}
+
+// What infini_rocm_matmul_grouped would launch for this problem on `num_cu` CUs under `variant` (-1: the heuristic) and `compute_type`,
+// given the low four address bits of the operands: gemm_plan without a runtime or a GPU. *splits is 1 unless the answer is split-K.
+int infini_rocm_matmul_plan_route(int dtype, int64_t batch, int64_t m, int64_t n, int64_t k, int trans_a, int trans_b, int64_t stride_a,
+                                  int64_t stride_b, int64_t stride_c, int has_bias, int64_t bias_stride_m, int64_t bias_stride_n, int act,
+                                  int64_t head_dim, int compute_type, int variant, int num_cu, int a_lo, int b_lo, int c_lo,
+                                  const char **name, int *splits) {
+    IROCM_CHECK_ARG(name && splits, "NULL argument");
+    IROCM_CHECK_ARG(variant >= -1 && variant < kNumVariants && compute_type >= 0 && compute_type <= 2 && num_cu > 0,
+                    "matmul: bad variant %d / compute type %d / CU count %d", variant, compute_type, num_cu);
+    const int64_t seq = head_dim ? (m > 0 ? m : 1) : 0; // one head-split block: routing reads head_dim only
+    if (const int st = matmul_check_args(dtype, batch, m, n, k, stride_c, act, seq, head_dim); st != INFINI_ROCM_OK)
+        return st;
+    *name = "none";
+    *splits = 0;
+    if (batch == 0 || m == 0 || n == 0)
+        return INFINI_ROCM_OK;
+    GemmProblem q = gemm_problem(matmul_args(batch, m, n, k, trans_a, trans_b, stride_a, stride_b, stride_c, 0, bias_stride_m, bias_stride_n,
+                                             act, seq, head_dim),
+                                 dtype, !trans_a, trans_b != 0, stride_c != 0);
+    q.bias = has_bias != 0;
+    q.a_lo = a_lo & 15; q.b_lo = b_lo & 15; q.c_lo = c_lo & 15;
+    const GemmPlan plan = gemm_plan(q, variant, compute_type, num_cu);
+    *name = matmul_variant_name(plan.variant);
+    *splits = plan.splits;
     return INFINI_ROCM_OK;
 }
 
@@ -762,7 +660,7 @@ int infini_rocm_probe_gemm_timeline(infiniRocmRuntime_t rt, const void *a, const
     p.m = (int)m; p.n = (int)n; p.k = (int)k; p.batch = 1;
     p.a_rs = k; p.a_cs = 1; p.b_rs = n; p.b_cs = 1;
     p.splitk = 1; p.epi16 = 1; p.zeros = rt->zeros;
-    IROCM_CHECK_ARG(gemm256_supported(p, true, false), "probe: shape not served by the 256-row kernels");
+    IROCM_CHECK_ARG(gemm256_supported(gemm_problem(p, INFINI_DT_BF16, true, false)), "probe: shape not served by the 256-row kernels");
     return g256p::launch_gemm256p_trace(rt, INFINI_DT_BF16, p, tile_cols / 64, (unsigned long long *)trace);
 }
 

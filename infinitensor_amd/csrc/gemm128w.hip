@@ -400,23 +400,6 @@ __global__ __launch_bounds__(256, 1) void gemm128w_kernel(WArgs pw) {
     }
 }
 
-bool supported(const GemmArgs &p) {
-    if (p.m <= 0 || p.n <= 0 || p.k < 128 || p.m % 256 || p.n % 256 || p.k % 128)
-        return false;
-    if (p.bias || p.act != 0 || p.hs_d != 0 || p.splitk > 1)
-        return false;
-    if ((((uintptr_t)p.a) | ((uintptr_t)p.b) | ((uintptr_t)p.c)) & 15)
-        return false;
-    if ((p.a_bs % 8) || (p.b_bs % 8) || (p.c_bs % 8))
-        return false;
-    // per-lane piece offsets are 32-bit: 256 rows of the major index must stay below 4 GiB
-    const long lda = p.a_cs == 1 ? p.a_rs : p.a_cs, ldb = p.b_rs == 1 ? p.b_cs : p.b_rs;
-    if (lda * 512 >= (1ll << 32) || ldb * 512 >= (1ll << 32) || (long)p.n * 32 >= (1ll << 32))
-        return false;
-    const long tiles = (long)(p.m / 256) * (p.n / 256) * p.batch;
-    return tiles < (1ll << 31);
-}
-
 template <typename Tr> static int launch_t(infiniRocmRuntime_t rt, GemmArgs p, bool akm, bool bkm) {
     WArgs w;
     p.tiles_m = p.m / 256;
@@ -426,22 +409,18 @@ template <typename Tr> static int launch_t(infiniRocmRuntime_t rt, GemmArgs p, b
     const char *dbg = getenv("IROCM_W128_DBG");
     w.dbg = dbg ? atoi(dbg) : 0;
     const unsigned grid = (unsigned)(w.total_tiles < rt->num_cu ? w.total_tiles : rt->num_cu);
-#define IROCM_G128W(AK, BK_)                                                                                         \
-    do {                                                                                                             \
-        auto kern = gemm128w_kernel<Tr, AK, BK_>;                                                                    \
-        IROCM_LDS_ATTR(kern, kLds, rt);                                                                              \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), kLds, rt->stream, w);                                        \
-    } while (0)
-    if (akm && bkm) IROCM_G128W(true, true);
-    else if (akm && !bkm) IROCM_G128W(true, false);
-    else if (!akm && bkm) IROCM_G128W(false, true);
-    else IROCM_G128W(false, false);
-#undef IROCM_G128W
-    IROCM_LAUNCH_CHECK("gemm128w");
-    return INFINI_ROCM_OK;
+    return with_layout(akm, bkm, [&](auto ak, auto bk) -> int {
+        auto kern = gemm128w_kernel<Tr, decltype(ak)::value, decltype(bk)::value>;
+        IROCM_LDS_ATTR(kern, kLds, rt);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), kLds, rt->stream, w);
+        IROCM_LAUNCH_CHECK("gemm128w");
+        return INFINI_ROCM_OK;
+    });
 }
 
 int launch_gemm128w(infiniRocmRuntime_t rt, int dtype, const GemmArgs &p, bool akm, bool bkm) {
+    if (!wave128_supported(gemm_problem(p, dtype, akm, bkm)))
+        IROCM_FAIL(INFINI_ROCM_UNSUPPORTED, "gemm128w: this problem is outside the four-wave kernel's contract (gemm_route.h)");
     return dtype == INFINI_DT_BF16 ? launch_t<Bf16Traits>(rt, p, akm, bkm) : launch_t<F16Traits>(rt, p, akm, bkm);
 }
 

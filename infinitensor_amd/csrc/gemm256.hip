@@ -398,25 +398,6 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(GemmArgs p) {
 
 } // namespace g256
 
-static bool al16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
-
-bool gemm256_supported(const GemmArgs &p, bool akm, bool bkm) {
-    if (p.k % g256::BK != 0 || p.k < g256::BK)
-        return false;
-    if (!al16(p.a) || !al16(p.b) || (p.a_bs % 8) || (p.b_bs % 8))
-        return false;
-    if (!akm && (p.m % 8 != 0 || p.m < 8))
-        return false;
-    if (!bkm && (p.n % 8 != 0 || p.n < 8))
-        return false;
-    if ((((uintptr_t)p.c) & 7) != 0)
-        return false;
-    // per-lane DMA offsets are 32-bit byte offsets inside one operand matrix
-    if ((long)p.m * p.k >= (1l << 31) || (long)p.n * p.k >= (1l << 31))
-        return false;
-    return true;
-}
-
 // Split-K launch: `splits` workgroups per output tile + one reduce pass. For shapes whose 256^2 tiles cannot fill the
 // 256 CUs (a 2048-token activation times a 4096-wide weight is 128 tiles) but whose K is long.
 template <typename Tr> static int launch256_splitk(infiniRocmRuntime_t rt, GemmArgs p, bool akm, bool bkm, int splits) {
@@ -433,18 +414,15 @@ template <typename Tr> static int launch256_splitk(infiniRocmRuntime_t rt, GemmA
     p.splitk = splits;
     p.partial = (float *)ws;
     const unsigned grid = (unsigned)p.tiles_m * p.tiles_n * p.batch * splits;
-#define IROCM_G256S(AK, BK_)                                                                       \
-    do {                                                                                           \
-        auto kern = g256::gemm256_kernel<Tr, AK, BK_, true>;                                    \
-        IROCM_LDS_ATTR(kern, g256::LDS_BYTES, rt);                                                 \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), g256::LDS_BYTES, rt->stream, p);           \
-    } while (0)
-    if (akm && bkm) IROCM_G256S(true, true);
-    else if (akm && !bkm) IROCM_G256S(true, false);
-    else if (!akm && bkm) IROCM_G256S(false, true);
-    else IROCM_G256S(false, false);
-#undef IROCM_G256S
-    IROCM_LAUNCH_CHECK("gemm256_splitk");
+    st = with_layout(akm, bkm, [&](auto ak, auto bk) -> int {
+        auto kern = g256::gemm256_kernel<Tr, decltype(ak)::value, decltype(bk)::value, true>;
+        IROCM_LDS_ATTR(kern, g256::LDS_BYTES, rt);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), g256::LDS_BYTES, rt->stream, p);
+        IROCM_LAUNCH_CHECK("gemm256_splitk");
+        return INFINI_ROCM_OK;
+    });
+    if (st != INFINI_ROCM_OK)
+        return st;
     const long items = (long)p.batch * p.m * p.n / ((p.n % 4 == 0) ? 4 : 1);
     long g = ceil_div(items, 256);
     if (g > (long)rt->num_cu * 16) g = (long)rt->num_cu * 16;
@@ -502,18 +480,15 @@ template <typename Tr> static int launch256_f32out(infiniRocmRuntime_t rt, GemmA
     p.splitk = splits;
     p.partial = direct ? (float *)p.c : planes;
     const unsigned grid = (unsigned)p.tiles_m * p.tiles_n * p.batch * splits;
-#define IROCM_G256F(AK, BK_)                                                                       \
-    do {                                                                                           \
-        auto kern = g256::gemm256_kernel<Tr, AK, BK_, true>;                                       \
-        IROCM_LDS_ATTR(kern, g256::LDS_BYTES, rt);                                                 \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), g256::LDS_BYTES, rt->stream, p);           \
-    } while (0)
-    if (akm && bkm) IROCM_G256F(true, true);
-    else if (akm && !bkm) IROCM_G256F(true, false);
-    else if (!akm && bkm) IROCM_G256F(false, true);
-    else IROCM_G256F(false, false);
-#undef IROCM_G256F
-    IROCM_LAUNCH_CHECK("gemm256_f32out");
+    const int st = with_layout(akm, bkm, [&](auto ak, auto bk) -> int {
+        auto kern = g256::gemm256_kernel<Tr, decltype(ak)::value, decltype(bk)::value, true>;
+        IROCM_LDS_ATTR(kern, g256::LDS_BYTES, rt);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), g256::LDS_BYTES, rt->stream, p);
+        IROCM_LAUNCH_CHECK("gemm256_f32out");
+        return INFINI_ROCM_OK;
+    });
+    if (st != INFINI_ROCM_OK)
+        return st;
     if (direct)
         return INFINI_ROCM_OK;
     const long items = (long)p.batch * p.m * p.n / ((p.n % 4 == 0) ? 4 : 1);
@@ -533,19 +508,13 @@ template <typename Tr> static int launch256(infiniRocmRuntime_t rt, GemmArgs p, 
     p.tiles_m = (int)ceil_div(p.m, g256::BM);
     p.tiles_n = (int)ceil_div(p.n, g256::BN);
     const unsigned grid = (unsigned)p.tiles_m * p.tiles_n * p.batch;
-#define IROCM_G256(AK, BK_)                                                                        \
-    do {                                                                                           \
-        auto kern = g256::gemm256_kernel<Tr, AK, BK_>;                                      \
-        IROCM_LDS_ATTR(kern, g256::LDS_BYTES, rt);                                                 \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), g256::LDS_BYTES, rt->stream, p);           \
-    } while (0)
-    if (akm && bkm) IROCM_G256(true, true);
-    else if (akm && !bkm) IROCM_G256(true, false);
-    else if (!akm && bkm) IROCM_G256(false, true);
-    else IROCM_G256(false, false);
-#undef IROCM_G256
-    IROCM_LAUNCH_CHECK("gemm256");
-    return INFINI_ROCM_OK;
+    return with_layout(akm, bkm, [&](auto ak, auto bk) -> int {
+        auto kern = g256::gemm256_kernel<Tr, decltype(ak)::value, decltype(bk)::value>;
+        IROCM_LDS_ATTR(kern, g256::LDS_BYTES, rt);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), g256::LDS_BYTES, rt->stream, p);
+        IROCM_LAUNCH_CHECK("gemm256");
+        return INFINI_ROCM_OK;
+    });
 }
 
 int launch_gemm256(infiniRocmRuntime_t rt, int dtype, const GemmArgs &p, bool akm, bool bkm) {

@@ -2,6 +2,7 @@
 // One translation unit for the three tile widths (A K-major, B gathered from NCHW: one layout each).
 #include "gemm256p_kernel.h"
 #include "conv_internal.h"
+#include "gemm_route.h" // persist_pick_nt
 
 namespace irocm {
 namespace g256p {

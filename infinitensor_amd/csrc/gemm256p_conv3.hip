@@ -3,6 +3,7 @@
 // (cuDNN cross-correlation, NCHW x FCRS), output extent src/operators/conv.cc:98-101.
 #include "gemm256p_kernel.h"
 #include "conv_internal.h"
+#include "gemm_route.h" // persist_pick_nt
 
 namespace irocm {
 namespace g256p {

@@ -1603,7 +1603,7 @@ static int launch_p(infiniRocmRuntime_t rt, GemmArgs g, bool akm, bool bkm, unsi
     pa.trace_fine = (TRACE && getenv("IROCM_GEMM_TRACE_FINE")) ? atoi(getenv("IROCM_GEMM_TRACE_FINE")) : 0;
     pa.split = 1; pa.slab = nullptr; pa.slab_bytes = 0; pa.flags = nullptr; pa.err = nullptr;
     constexpr int kLds = LDS_BYTES + (TRACE ? kTraceBytes : 0) + kExtraLds;
-    if (!(g.act == 0 || g.act == 1 || g.act == 5) || (g.bias && !(g.bias_m == 0 && g.bias_n == 1)))
+    if (!persist_epilogue_ok(gemm_problem(g, Tr::kDType, akm, bkm)))
         IROCM_FAIL(INFINI_ROCM_UNSUPPORTED, "gemm256p: activation %d / this bias layout is not served by the persistent kernels", g.act);
     g.tiles_m = (int)ceil_div(g.m, BM);
     g.tiles_n = (int)ceil_div(g.n, 64 * NT);
@@ -1625,25 +1625,20 @@ static int launch_p(infiniRocmRuntime_t rt, GemmArgs g, bool akm, bool bkm, unsi
     const unsigned cus = (unsigned)(rt->num_cu >= 8 ? (rt->num_cu / 8) * 8 : rt->num_cu);
     if (grid > cus)
         grid = cus;
-#define IROCM_G256P(AK, BK_)                                                                       \
-    do {                                                                                           \
-        auto kern = gemm256p_kernel<Tr, AK, BK_, NT, TRACE>;                                       \
-        IROCM_LDS_ATTR(kern, kLds, rt);                                                            \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), kLds, rt->stream, pa);                     \
-    } while (0)
+    auto launch = [&](auto ak, auto bk) -> int {
+        auto kern = gemm256p_kernel<Tr, decltype(ak)::value, decltype(bk)::value, NT, TRACE>;
+        IROCM_LDS_ATTR(kern, kLds, rt);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), kLds, rt->stream, pa);
+        IROCM_LAUNCH_CHECK("gemm256p");
+        return INFINI_ROCM_OK;
+    };
     if constexpr (TRACE) { // the timeline build exists for the ONNX "NN" layout only
         if (!(akm && !bkm))
             IROCM_FAIL(INFINI_ROCM_UNSUPPORTED, "gemm timeline: NN layout only");
-        IROCM_G256P(true, false);
+        return launch(std::true_type{}, std::false_type{});
     } else {
-        if (akm && bkm) IROCM_G256P(true, true);
-        else if (akm && !bkm) IROCM_G256P(true, false);
-        else if (!akm && bkm) IROCM_G256P(false, true);
-        else IROCM_G256P(false, false);
+        return with_layout(akm, bkm, launch);
     }
-#undef IROCM_G256P
-    IROCM_LAUNCH_CHECK("gemm256p");
-    return INFINI_ROCM_OK;
 }
 
 // conv mode: one instantiation per tile width and residual flag (A K-major, B gathered by pixel slots)

@@ -580,20 +580,6 @@ template <int T, bool TM, bool TRACE = false> __global__ __launch_bounds__(256, 
 
 } // namespace f32k
 
-static bool al16p(const void *p) { return (((uintptr_t)p) & 15) == 0; }
-
-// A K-major with 16-byte rows; B K-major or N-major with 16-byte rows; K a multiple of 4 (a K tail inside the last
-// 32-wide tile is zero-filled); the generic kernel serves the rest
-bool fast32_supported(const GemmArgs &p, bool akm, bool bkm) {
-    if (!akm || p.k % 4 != 0 || p.k < 4 || p.m < 1 || p.n < 4)
-        return false;
-    if (!al16p(p.a) || !al16p(p.b) || (p.a_bs % 4) || (p.b_bs % 4) || (p.a_rs % 4))
-        return false;
-    if (bkm ? (p.b_cs % 4 != 0) : (p.b_rs % 4 != 0 || p.n % 4 != 0))
-        return false;
-    return true;
-}
-
 // small != 0: 64^2 tiles (a problem with fewer than ~half a 128^2 tile per CU)
 int launch_fast32(infiniRocmRuntime_t rt, GemmArgs p, bool bkm, int small) {
     const int bm = small ? 64 : 128;
@@ -632,7 +618,7 @@ int launch_conv_igemm32(infiniRocmRuntime_t rt, const void *x, const void *w, co
     // (k-major rows whose length is not a multiple of 4 — the 3-channel 7 x 7 stem: 147 — are copied into zero-padded 16-byte rows)
     const bool padk = !tm && (c * r * s) % 4 != 0;
     const int64_t k = tm ? cp * r * s : (c * r * s + 3) / 4 * 4;
-    if (k < 4 || (!tm && !padk && !al16p(w)) || (((uintptr_t)w) & 3) != 0 || (((uintptr_t)x) & 3) != 0 || (((uintptr_t)y) & 3) != 0 || (res && (((uintptr_t)res) & 3) != 0))
+    if (k < 4 || (!tm && !padk && !aligned16((uintptr_t)w)) || (((uintptr_t)w) & 3) != 0 || (((uintptr_t)x) & 3) != 0 || (((uintptr_t)y) & 3) != 0 || (res && (((uintptr_t)res) & 3) != 0))
         return -1;
     if (n * c * h * wd * 4 >= (1ll << 31) - 64 || ncols >= (1ll << 31) - 256 || n * f * oh * ow >= (1ll << 31) || k >= (1ll << 24))
         return -1;

@@ -1,6 +1,8 @@
 // Shared device helpers for the MFMA GEMM / implicit-GEMM conv kernels (gfx950 only).
 #pragma once
 #include "common.h"
+#include "gemm_route.h"
+#include <type_traits>
 
 namespace irocm {
 
@@ -63,6 +65,20 @@ struct GemmArgs {
                           // (computed in the kernel — a division — hipcc kept it in vector registers and wrapped every buffer load of
                           // the residual in a readfirstlane waterfall loop)
 };
+
+// what the planner (gemm_route.h) reads of a filled GemmArgs; akm / bkm: A / B stored with k contiguous
+inline GemmProblem gemm_problem(const GemmArgs &p, int dtype, bool akm, bool bkm, bool c_grouped = false) {
+    return {dtype, p.batch, p.m, p.n, p.k, akm, bkm, akm ? p.a_rs : p.a_cs, bkm ? p.b_cs : p.b_rs, p.a_bs, p.b_bs, p.c_bs, c_grouped,
+            p.bias != nullptr, p.bias_m, p.bias_n, p.act, p.hs_d,
+            (unsigned)((uintptr_t)p.a & 15), (unsigned)((uintptr_t)p.b & 15), (unsigned)((uintptr_t)p.c & 15)};
+}
+
+// the run-time operand layout as two compile-time flags: f(std::bool_constant<akm>, std::bool_constant<bkm>)
+template <typename F> inline int with_layout(bool akm, bool bkm, F &&f) {
+    if (akm)
+        return bkm ? f(std::true_type{}, std::true_type{}) : f(std::true_type{}, std::false_type{});
+    return bkm ? f(std::false_type{}, std::true_type{}) : f(std::false_type{}, std::false_type{});
+}
 
 // element offset of C(row, col) inside one batch's [m x n] block
 __device__ __forceinline__ long c_off(const GemmArgs &p, long row, long col) {

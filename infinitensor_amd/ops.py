@@ -202,6 +202,23 @@ def conv_plan_route(dtype: torch.dtype, n: int, c: int, h: int, w: int, f: int, 
     return route.value.decode(), form.value.decode()
 
 
+def matmul_plan_route(dtype: torch.dtype, batch: int, m: int, n: int, k: int, trans_a: bool = False, trans_b: bool = False,
+                      stride_a: int | None = None, stride_b: int | None = None, stride_c: int = 0, bias: bool = False, bias_stride_m: int = 0,
+                      bias_stride_n: int = 1, act: int = 0, head_dim: int = 0, compute_type: str = "default", variant: int = -1,
+                      num_cu: int = 256, a_lo: int = 0, b_lo: int = 0, c_lo: int = 0) -> tuple[str, int]:
+    """(variant name, split-K factor) matmul would launch for this problem (infini_rocm_matmul_plan_route: pure, no GPU). Batch strides
+    default to the contiguous ones (None), `*_lo` are the operands' low four address bits (data_ptr() & 15)."""
+    import ctypes as C
+
+    name, splits = C.c_char_p(), C.c_int()
+    check(lib().infini_rocm_matmul_plan_route(int(_TORCH2DT[dtype]), batch, m, n, k, int(trans_a), int(trans_b),
+                                              m * k if stride_a is None else stride_a, n * k if stride_b is None else stride_b, stride_c,
+                                              int(bias), bias_stride_m, bias_stride_n, int(act), head_dim,
+                                              {"default": 0, "tf32": 0, "bf16": 1, "fp16": 2}[compute_type], int(variant), int(num_cu),
+                                              int(a_lo), int(b_lo), int(c_lo), C.byref(name), C.byref(splits)))
+    return name.value.decode(), splits.value
+
+
 def set_conv_variant(rt: RocmRuntime, variant: int) -> None:
     """-1 heuristic, 1 generic implicit GEMM, 2 conv_s1 wherever eligible, 3 batched-GEMM route for pointwise, 4 = 2 without the patch
     kernel, 5 pointwise layers as one pixel-slot GEMM, 6 = 2 with the 8-wave patch kernel, 7 3 x 3 layers as one tap GEMM (include/infini_rocm.h;

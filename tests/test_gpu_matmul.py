@@ -307,6 +307,43 @@ def test_matmul_fp32_heuristic_picks_the_tile_kernel_for_large_problems(rt):
     assert ops.matmul_last_variant(rt) == "generic64"
 
 
+ROUTE_SHAPES = [
+    # b, m, n, k — the smallest shapes that reach split-K, a persistent kernel, the four-wave kernel and every fall-back edge
+    (1, 256, 256, 128),
+    (1, 300, 256, 256),
+    (3, 130, 132, 100),
+    (1, 33, 48, 64),
+    (1, 1024, 1024, 1024),
+    (1, 4096, 2048, 64),
+]
+
+
+def test_plan_route_agrees_with_the_launch(rt):
+    """infini_rocm_matmul_plan_route (csrc/gemm_route.h, the planner tests/test_matmul_route_cpu.py asks without a GPU) names the kernel
+    a launch reports, for the heuristic and every forced variant, bf16 and fp32, and for an A operand that starts 8 bytes off a
+    16-byte boundary. Results are not re-checked here: the tests above do that."""
+    cus = rt.device_info()["compute_units"]
+    for dtype in (torch.bfloat16, torch.float32):
+        off = 8 // torch.empty((), dtype=dtype).element_size()
+        for b, m, n, k in ROUTE_SHAPES:
+            flat = torch.randn(b * m * k + off, device="cuda").to(dtype)
+            bm = torch.randn(b, k, n, device="cuda").to(dtype)
+            for a in (flat[:b * m * k].view(b, m, k), flat[off:].view(b, m, k)):
+                for variant in range(-1, 9):
+                    ops.set_matmul_variant(rt, variant)
+                    try:
+                        c = ops.matmul(rt, a, bm)
+                        got = ops.matmul_last_variant(rt)
+                    finally:
+                        ops.set_matmul_variant(rt, -1)
+                    # (a batch of one is launched with zero batch strides: matmul.cc:124-137)
+                    plan = ops.matmul_plan_route(dtype, b, m, n, k, stride_a=m * k if b > 1 else 0, stride_b=n * k if b > 1 else 0,
+                                                 variant=variant, num_cu=cus, a_lo=a.data_ptr() & 15, b_lo=bm.data_ptr() & 15,
+                                                 c_lo=c.data_ptr() & 15)
+                    assert got == plan[0], (dtype, (b, m, n, k), variant, a.data_ptr() & 15)
+    rt.sync()
+
+
 def test_matmul_bias_broadcast_forms(rt):
     """bias broadcast into C like the reference (matmul.cc:86-118): [n], [m,n], [1], [b,m,n]."""
     rng = np.random.default_rng(11)
