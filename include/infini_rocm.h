@@ -193,8 +193,36 @@ int infini_rocm_matmul(infiniRocmRuntime_t rt, int dtype, const void *a, const v
  * exact fp32 (gfx950 has no xf32 matrix instruction; more accurate than asked). 1 = "bf16", 2 = "fp16": A and B are converted
  * once (workspace) and multiplied on the 16-bit MFMA path with fp32 accumulation and fp32 output (~10x the exact kernel's
  * rate) wherever that kernel serves the shape (K % 64 == 0, 16-byte aligned rows), else exactly. Sticky per runtime until
- * reset to 0; 16-bit MatMuls ignore it. */
+ * reset to 0; 16-bit MatMuls ignore it.
+ *
+ * 3 = "bf16x3", 4 = "bf16x6": fp32-like results at the bf16 MFMA's rate. Every value x of A and B is written as a sum of bf16
+ * pieces, rne = round-to-nearest-even to bf16: p0 = rne(x), p1 = rne(x - p0), and for "bf16x6" p2 = rne((x - p0) - p1); both
+ * subtractions are exact in fp32. "bf16x3" sums the three products a0 b0 + a0 b1 + a1 b0 (only a1 b1 is dropped), "bf16x6" the six
+ * a_i b_j with i + j <= 2, in ONE launch of the bf16 kernel over K' = 3 K (6 K): the products lie side by side along K
+ * (infini_rocm_split_bf16 writes the operands that way), sums and output are fp32.
+ * Accuracy. bf16 keeps 8 significant bits: |x - p0| <= 2^-8 |x|, |x - p0 - p1| <= 2^-16 |x|, |x - p0 - p1 - p2| <= 2^-24 |x|.
+ *   "bf16x3": per product at most 3 * 2^-16 |a| |b| is missing, so |C - A B|_ij <= 3 * 2^-16 (|A| |B|)_ij plus the summation error of
+ *     an fp32 GEMM over 3 K terms — about 16 good bits where "bf16" has 8 and tf32 would have 10. Typically far better (N(0, 1) data:
+ *     0.1 * 2^-16 (|A| |B|)).
+ *   "bf16x6": per product at most ~4 * 2^-24 |a| |b|, below the fp32 summation error: as good as the exact kernel.
+ * Inf / NaN: a p0 that is not finite (x is Inf or NaN, or a finite x that rounds up to bf16's Inf: |x| >= 2^128 - 2^119) gets lower
+ *   pieces of 0: the split itself never turns an Inf into NaN by Inf - Inf. In the PRODUCT an Inf still meets lower pieces of the
+ *   other operand, and one of those that is exactly 0 gives Inf * 0: outputs that depend on an Inf may be NaN where the exact kernel
+ *   gives Inf. NaN stays NaN.
+ * Subnormals: the bits of a lower piece that fall below bf16's smallest subnormal (2^-133) are lost, which happens to values of
+ *   magnitude around 2^-110 and smaller; the result is still at least "bf16"-accurate there.
+ * A problem the path cannot serve (K % 64 != 0, an A or B that is not 16-byte aligned, a batch stride that is neither 0 nor one block,
+ *   a head-split or grouped output, a C that is not 16-byte aligned, m * K' or n * K' >= 2^31) runs the EXACT kernels: never less
+ *   accurate than asked. */
 int infini_rocm_matmul_set_compute_type(infiniRocmRuntime_t rt, int compute_type);
+/* The input pass of "bf16x3" / "bf16x6", on its own: x is `blocks` dense fp32 matrices [rows][cols]; y receives `terms` (1 to 6) bf16
+ * planes per matrix, plane t holding piece plane_piece[t] (0, 1 or 2: p0, p1, p2 above) of every element, laid out as a GEMM with
+ * K' = terms * K reads the operand:
+ *   k_is_cols != 0 (K = cols, a K-major operand): y is [blocks][rows][terms * cols], plane t at column offset t * cols;
+ *   k_is_cols == 0 (K = rows):                    y is [blocks][terms * rows][cols], plane t at row offset t * rows.
+ * cols % 8 == 0, x and y 16-byte aligned (16-byte loads and stores), else INFINI_ROCM_INVALID_ARGUMENT. */
+int infini_rocm_split_bf16(infiniRocmRuntime_t rt, const void *x, void *y, int64_t blocks, int64_t rows, int64_t cols, int k_is_cols,
+                           int terms, const int *plane_piece);
 /* MatMul whose result is stored head-split: the [m x n] block of every batch entry is written as
  * [m / seq][n / head_dim][seq][head_dim], i.e. MatMul -> Reshape([B, S, H, D]) -> Transpose(0, 2, 1, 3) — the q / k / v
  * projection of a transformer layer as ONNX exporters emit it (reference: matmul.cc + CopyCuda reshape.cc:4-13 +

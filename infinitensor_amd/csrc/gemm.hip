@@ -450,21 +450,39 @@ static int launch_generic64(infiniRocmRuntime_t rt, int dtype, GemmArgs p) {
     return INFINI_ROCM_OK;
 }
 
-// The reduced-precision compute types of an fp32 MatMul (gemm_reduced_precision_ok): A and B are cast once into the workspace —
+// The reduced-precision compute types of an fp32 MatMul (gemm_reduced_precision_ok): A and B are converted once into the workspace —
 // (stride ? batch : 1) dense blocks each — and the split-K kernel writes fp32. The plan was made on shape and alignment alone, so
-// the workspace is grown only for a problem that takes this path.
+// the workspace is grown only for a problem that takes this path. "bf16" / "fp16" cast; "bf16x3" / "bf16x6" write `terms` bf16 planes
+// per operand (split.hip) and the same kernel runs on K' = terms * K.
 static int launch_f32_reduced(infiniRocmRuntime_t rt, int compute_type, GemmArgs p, bool akm, bool bkm, int splits) {
-    const int dt16 = compute_type == 1 ? INFINI_DT_BF16 : INFINI_DT_F16;
-    const int64_t mk = (int64_t)p.m * p.k, nk = (int64_t)p.n * p.k, mn = (int64_t)p.m * p.n;
+    const int dt16 = compute_type == 2 ? INFINI_DT_F16 : INFINI_DT_BF16;
+    const int terms = gemm_split_terms(compute_type);
+    const int64_t k = p.k, kp = (int64_t)terms * k;
+    const int64_t mk = (int64_t)p.m * kp, nk = (int64_t)p.n * kp, mn = (int64_t)p.m * p.n;
     const bool a_shared = p.a_bs == 0 || p.batch == 1, b_shared = p.b_bs == 0 || p.batch == 1;
-    const int64_t na = (a_shared ? 1 : p.batch) * mk, nb = (b_shared ? 1 : p.batch) * nk;
+    const int64_t a_blocks = a_shared ? 1 : p.batch, b_blocks = b_shared ? 1 : p.batch;
+    const int64_t na = a_blocks * mk, nb = b_blocks * nk;
     const size_t a_bytes = ((size_t)na * 2 + 255) & ~(size_t)255, b_bytes = ((size_t)nb * 2 + 255) & ~(size_t)255;
     char *ws = nullptr;
     int st = infini_rocm_workspace(rt, a_bytes + b_bytes + (size_t)splits * p.batch * mn * sizeof(float), (void **)&ws);
-    if (st == INFINI_ROCM_OK)
+    if (st != INFINI_ROCM_OK)
+        return st;
+    if (terms == 1) {
         st = infini_rocm_cast(rt, INFINI_DT_F32, dt16, p.a, ws, na);
-    if (st == INFINI_ROCM_OK)
-        st = infini_rocm_cast(rt, INFINI_DT_F32, dt16, p.b, ws + a_bytes, nb);
+        if (st == INFINI_ROCM_OK)
+            st = infini_rocm_cast(rt, INFINI_DT_F32, dt16, p.b, ws + a_bytes, nb);
+    } else {
+        // A is stored [m][k] (K-major) or [k][m]; B [n][k] (K-major) or [k][n]
+        const int table = compute_type - 3;
+        st = infini_rocm_split_bf16(rt, p.a, ws, a_blocks, akm ? p.m : k, akm ? k : p.m, akm ? 1 : 0, terms, kSplitPieceA[table]);
+        if (st == INFINI_ROCM_OK)
+            st = infini_rocm_split_bf16(rt, p.b, ws + a_bytes, b_blocks, bkm ? p.n : k, bkm ? k : p.n, bkm ? 1 : 0, terms, kSplitPieceB[table]);
+        p.k = (int)kp;
+        if (akm)
+            p.a_rs = kp;
+        if (bkm)
+            p.b_cs = kp;
+    }
     if (st != INFINI_ROCM_OK)
         return st;
     p.a = ws;
@@ -493,11 +511,13 @@ int infini_rocm_matmul_last_variant(infiniRocmRuntime_t rt, int *variant) {
 // MatmulObj::getComputeType() (reference: matmul.cc:51-64 — "tf32" / "fp16" / "bf16" select cuBLAS compute types whose PRODUCTS
 // take reduced-precision inputs while sums and outputs stay fp32). 0 "default" / "tf32": exact fp32 products (gfx950 has no
 // xf32 MFMA; more accurate than asked). 1 "bf16", 2 "fp16": an fp32 MatMul converts A and B once into the workspace and runs the
-// 16-bit MFMA kernel with fp32 accumulation and fp32 output — the reference's opt-in ~10x over exact fp32. Sticky per runtime
-// (the plugin sets it around the one launch); ignored for 16-bit operands.
+// 16-bit MFMA kernel with fp32 accumulation and fp32 output — the reference's opt-in ~10x over exact fp32. 3 "bf16x3", 4 "bf16x6":
+// the same kernel on two / three bf16 pieces per value, the cross products side by side along K (gemm_route.h; include/infini_rocm.h
+// has the accuracy statement). Sticky per runtime (the plugin sets it around the one launch); ignored for 16-bit operands.
 int infini_rocm_matmul_set_compute_type(infiniRocmRuntime_t rt, int compute_type) {
     IROCM_CHECK_ARG(rt, "NULL runtime");
-    IROCM_CHECK_ARG(compute_type >= 0 && compute_type <= 2, "compute type %d: 0 default / tf32, 1 bf16, 2 fp16", compute_type);
+    IROCM_CHECK_ARG(compute_type >= 0 && compute_type < kComputeTypes, "compute type %d: 0 default / tf32, 1 bf16, 2 fp16, 3 bf16x3, 4 bf16x6",
+                    compute_type);
     rt->matmul_compute_type = compute_type;
     return INFINI_ROCM_OK;
 }
@@ -627,7 +647,7 @@ int infini_rocm_matmul_plan_route(int dtype, int64_t batch, int64_t m, int64_t n
                                   int64_t head_dim, int compute_type, int variant, int num_cu, int a_lo, int b_lo, int c_lo,
                                   const char **name, int *splits) {
     IROCM_CHECK_ARG(name && splits, "NULL argument");
-    IROCM_CHECK_ARG(variant >= -1 && variant < kNumVariants && compute_type >= 0 && compute_type <= 2 && num_cu > 0,
+    IROCM_CHECK_ARG(variant >= -1 && variant < kNumVariants && compute_type >= 0 && compute_type < kComputeTypes && num_cu > 0,
                     "matmul: bad variant %d / compute type %d / CU count %d", variant, compute_type, num_cu);
     const int64_t seq = head_dim ? (m > 0 ? m : 1) : 0; // one head-split block: routing reads head_dim only
     if (const int st = matmul_check_args(dtype, batch, m, n, k, stride_c, act, seq, head_dim); st != INFINI_ROCM_OK)

@@ -183,7 +183,7 @@ struct GemmPlan {
     MatmulVariant variant;  // what runs, and what infini_rocm_matmul_last_variant reports
     int splits;             // kGemmTile256SplitK: workgroups per tile (before empty slices are dropped), 1 otherwise
     bool fast32_small;      // kGemmFast32: 64^2 tiles instead of 128^2
-    bool reduced_precision; // fp32 operands cast to 16 bit in the workspace, the split-K kernel with fp32 output
+    bool reduced_precision; // fp32 operands cast (or split into bf16 pieces) in the workspace, the split-K kernel with fp32 output
 };
 
 // MatmulObj::getComputeType() 1 "bf16" / 2 "fp16" on an fp32 MatMul: 16-bit copies of A and B in the workspace, the 256^2 split-K
@@ -192,17 +192,44 @@ struct GemmPlan {
 // (batch strides: the casts copy (stride ? batch : 1) CONTIGUOUS blocks of m * k (n * k) elements, so the path is taken only
 // for operands that ARE such blocks — stride 0 (shared) or exactly one block; any other stride keeps the exact kernels.
 // Round-4 advisor: with another stride the cast read the wrong rows and the kernel indexed the 16-bit copy past its end.)
+//
+// 3 "bf16x3" / 4 "bf16x6": every fp32 value is written as a sum of two / three bf16 pieces (split.hip) and the cross products that
+// matter are laid SIDE BY SIDE ALONG K — A' = [A_p | ...], B' = [B_q | ...], one plane per term, K' = terms * K — so one launch of the
+// same bf16 kernel sums them all (and its split-K gets terms x more K to cut). Term t multiplies piece kSplitPieceA[t] of A with piece
+// kSplitPieceB[t] of B (piece 0 = the bf16 rounding, 1 and 2 the roundings of what is left): x3 drops only lo * lo, x6 has every pair
+// with i + j <= 2; the small products come first. The two tables are a PAIR: the same t must name one product on both sides.
+constexpr int kComputeTypes = 5; // 0 default / tf32, 1 bf16, 2 fp16, 3 bf16x3, 4 bf16x6
+constexpr int kSplitMaxTerms = 6;
+constexpr int kSplitPieceA[2][kSplitMaxTerms] = {{1, 0, 0, 0, 0, 0}, {1, 2, 0, 1, 0, 0}};
+constexpr int kSplitPieceB[2][kSplitMaxTerms] = {{0, 1, 0, 0, 0, 0}, {1, 0, 2, 0, 1, 0}};
+inline int gemm_split_terms(int compute_type) { return compute_type == 3 ? 3 : compute_type == 4 ? 6 : 1; }
+
+// The 16-bit problem the reduced-precision path hands to the 256^2 kernel: copies 256-byte aligned in the workspace, dense blocks,
+// K' = terms * K with the leading dimension of a K-major operand growing with it.
+inline GemmProblem gemm_reduced_problem(const GemmProblem &q, int compute_type) {
+    const int64_t terms = gemm_split_terms(compute_type);
+    GemmProblem q16 = q;
+    q16.k = terms * q.k;
+    q16.lda = q.akm ? q16.k : q.m;
+    q16.ldb = q.bkm ? q16.k : q.n;
+    q16.a_lo = q16.b_lo = 0;
+    q16.a_bs = (q.a_bs == 0 || q.batch == 1) ? 0 : q.m * q16.k;
+    q16.b_bs = (q.b_bs == 0 || q.batch == 1) ? 0 : q.n * q16.k;
+    return q16;
+}
 inline bool gemm_reduced_precision_ok(const GemmProblem &q, int compute_type) {
     if (q.dtype != INFINI_DT_F32 || compute_type == 0 || q.hs_d != 0 || q.c_grouped)
         return false;
     if (q.batch != 1 && !((q.a_bs == 0 || q.a_bs == q.m * q.k) && (q.b_bs == 0 || q.b_bs == q.n * q.k)))
         return false;
-    // the 16-bit copies: 256-byte aligned in the workspace, dense blocks
-    GemmProblem q16 = q;
-    q16.a_lo = q16.b_lo = 0;
-    q16.a_bs = (q.a_bs == 0 || q.batch == 1) ? 0 : q.m * q.k;
-    q16.b_bs = (q.b_bs == 0 || q.batch == 1) ? 0 : q.n * q.k;
-    return gemm256_supported(q16) && aligned16(q.c_lo);
+    // the split kernel reads its fp32 source in 16-byte runs (the casts of 1 / 2 take any address)
+    if (compute_type >= 3 && !(aligned16(q.a_lo) && aligned16(q.b_lo)))
+        return false;
+    // whole K-tiles of the ORIGINAL K too: K' % 64 == 0 alone would let a plane boundary fall inside a K-tile — harmless for the sums,
+    // but the contract stays the one of the 16-bit types
+    if (q.k % 64 != 0)
+        return false;
+    return gemm256_supported(gemm_reduced_problem(q, compute_type)) && aligned16(q.c_lo);
 }
 
 // `forced`: the runtime's variant (kGemmHeuristic or a kernel). A forced kernel that cannot serve the problem falls back the way the
@@ -211,7 +238,7 @@ inline GemmPlan gemm_plan(const GemmProblem &q, int forced, int compute_type, in
     GemmPlan pl = {kGemmGeneric64, 1, false, false};
     if (gemm_reduced_precision_ok(q, compute_type)) {
         pl.variant = kGemmTile256SplitK;
-        pl.splits = gemm_f32out_splits(q, num_cu);
+        pl.splits = gemm_f32out_splits(gemm_reduced_problem(q, compute_type), num_cu);
         pl.reduced_precision = true;
         return pl;
     }

@@ -135,10 +135,30 @@ def matmul(rt: RocmRuntime, a: torch.Tensor, b: torch.Tensor, bias: torch.Tensor
     return out
 
 
+# MatmulObj::getComputeType() strings -> infini_rocm_matmul_set_compute_type's argument
+_COMPUTE_TYPES = {"default": 0, "tf32": 0, "bf16": 1, "fp16": 2, "bf16x3": 3, "bf16x6": 4}
+
+
 def set_matmul_compute_type(rt: RocmRuntime, compute_type: str) -> None:
     """MatmulObj::getComputeType() for fp32 MatMuls: "default" / "tf32" exact fp32 products, "bf16" / "fp16" 16-bit products with
-    fp32 accumulation and output (infini_rocm_matmul_set_compute_type). Sticky until reset to "default"."""
-    check(lib().infini_rocm_matmul_set_compute_type(rt.handle, {"default": 0, "tf32": 0, "bf16": 1, "fp16": 2}[compute_type]))
+    fp32 accumulation and output, "bf16x3" / "bf16x6" two / three bf16 pieces per value and their three / six cross products on the
+    bf16 path (about 16 good bits / fp32-like; infini_rocm_matmul_set_compute_type). Sticky until reset to "default"."""
+    check(lib().infini_rocm_matmul_set_compute_type(rt.handle, _COMPUTE_TYPES[compute_type]))
+
+
+def split_bf16(rt: RocmRuntime, x: torch.Tensor, k_is_cols: bool, plane_piece: Sequence[int]) -> torch.Tensor:
+    """The input pass of "bf16x3" / "bf16x6" alone (infini_rocm_split_bf16): x is fp32 [..., rows, cols]; the result holds
+    len(plane_piece) bf16 planes per matrix, plane t = piece plane_piece[t] (0: rne(x), 1: rne of what is left, 2: again) —
+    [..., rows, terms * cols] with plane t at column t * cols if k_is_cols, else [..., terms * rows, cols] with plane t at row t * rows."""
+    if x.dtype != torch.float32 or x.dim() < 2:
+        raise ValueError("split_bf16 expects an fp32 tensor [..., rows, cols]")
+    rows, cols = x.shape[-2], x.shape[-1]
+    terms = len(plane_piece)
+    shape = list(x.shape[:-2]) + ([rows, terms * cols] if k_is_cols else [terms * rows, cols])
+    out = torch.empty(shape, dtype=torch.bfloat16, device=x.device)
+    check(lib().infini_rocm_split_bf16(rt.handle, _ptr(x), _ptr(out), x.numel() // max(1, rows * cols), rows, cols, int(bool(k_is_cols)),
+                                       terms, _i32arr([int(v) for v in plane_piece])))
+    return out
 
 
 def set_matmul_variant(rt: RocmRuntime, variant: int) -> None:
@@ -204,17 +224,19 @@ def conv_plan_route(dtype: torch.dtype, n: int, c: int, h: int, w: int, f: int, 
 
 def matmul_plan_route(dtype: torch.dtype, batch: int, m: int, n: int, k: int, trans_a: bool = False, trans_b: bool = False,
                       stride_a: int | None = None, stride_b: int | None = None, stride_c: int = 0, bias: bool = False, bias_stride_m: int = 0,
-                      bias_stride_n: int = 1, act: int = 0, head_dim: int = 0, compute_type: str = "default", variant: int = -1,
+                      bias_stride_n: int = 1, act: int = 0, head_dim: int = 0, compute_type: str | int = "default", variant: int = -1,
                       num_cu: int = 256, a_lo: int = 0, b_lo: int = 0, c_lo: int = 0) -> tuple[str, int]:
     """(variant name, split-K factor) matmul would launch for this problem (infini_rocm_matmul_plan_route: pure, no GPU). Batch strides
-    default to the contiguous ones (None), `*_lo` are the operands' low four address bits (data_ptr() & 15)."""
+    default to the contiguous ones (None), `*_lo` are the operands' low four address bits (data_ptr() & 15). compute_type: the
+    operator's string, or the library's number."""
     import ctypes as C
 
     name, splits = C.c_char_p(), C.c_int()
     check(lib().infini_rocm_matmul_plan_route(int(_TORCH2DT[dtype]), batch, m, n, k, int(trans_a), int(trans_b),
                                               m * k if stride_a is None else stride_a, n * k if stride_b is None else stride_b, stride_c,
                                               int(bias), bias_stride_m, bias_stride_n, int(act), head_dim,
-                                              {"default": 0, "tf32": 0, "bf16": 1, "fp16": 2}[compute_type], int(variant), int(num_cu),
+                                              compute_type if isinstance(compute_type, int) else _COMPUTE_TYPES[compute_type], int(variant),
+                                              int(num_cu),
                                               int(a_lo), int(b_lo), int(c_lo), C.byref(name), C.byref(splits)))
     return name.value.decode(), splits.value
 

@@ -148,6 +148,11 @@ class RocmTunableKernel : public Kernel {
 };
 
 // ---- MatMul (reference: matmulCublas, src/kernels/cuda/matmul.cc:66-209) --------------------------
+// MatmulObj::getComputeType() -> infini_rocm_matmul_set_compute_type: "bf16x3" / "bf16x6" are this backend's own (fp32-like results from
+// two / three bf16 pieces per value); anything else, "default" and "tf32" included, multiplies exactly
+static int computeTypeCode(const std::string &ct) {
+    return ct == "bf16" ? 1 : ct == "fp16" ? 2 : ct == "bf16x3" ? 3 : ct == "bf16x6" ? 4 : 0;
+}
 class MatmulRocm : public RocmTunableKernel {
     int setVariant(infiniRocmRuntime_t rt, int v) const override { return infini_rocm_matmul_set_variant(rt, v); }
     // fast128 (LDS-DMA 128^2), tile256 one-shot, tile256 split-K, persistent 256 / 192 / 128, and for fp32 the generic 64^2
@@ -169,7 +174,7 @@ class MatmulRocm : public RocmTunableKernel {
             sbias = dims64(op->getInputs(2)->getDims());
         }
         // getComputeType() (matmul.cc:51-64; onnx.py:41-47 passes `matmul_compute_type`): "bf16" / "fp16" ask for reduced-precision
-        // PRODUCTS of fp32 operands — honoured below (16-bit MFMA, fp32 sums and output); "default" and "tf32" multiply exactly
+        // PRODUCTS of fp32 operands — honoured below (16-bit MFMA, fp32 sums and output; "bf16x3" / "bf16x6": bf16 pieces); "default" and "tf32" multiply exactly
         // (gemm32.hip). `act` is not applied (the reference ignores it). What the launch plan folded into THIS MatMul arrives
         // through the overrides (rocm_fusion.cc): the row bias of a following Add (onnx.py:280-290 imports MatMul without
         // bias), a Gelu, a head-split store.
@@ -184,7 +189,7 @@ class MatmulRocm : public RocmTunableKernel {
                 if (set)
                     (void)infini_rocm_matmul_set_compute_type(rt, 0);
             }
-        } ctScope(H(ctx), A->getDType() == DataType::Float32 ? (op->getComputeType() == "bf16" ? 1 : (op->getComputeType() == "fp16" ? 2 : 0)) : 0);
+        } ctScope(H(ctx), A->getDType() == DataType::Float32 ? computeTypeCode(op->getComputeType()) : 0);
         const auto &ov = RocmRuntimeObj::overrides;
         const bool mine = ov.matmul == _op.get();
         if (mine && ov.biasPtr) {
