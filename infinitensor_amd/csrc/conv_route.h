@@ -4,6 +4,7 @@
 // pointers it cannot see qualify: alignment, 32-bit offset limits and hipMemGetAddressRange stay in the launchers, which return -1
 // ("declined") — the dispatcher then takes the next candidate.
 #pragma once
+#include "diag.h"
 #include "infini_rocm.h"
 #include <cstddef>
 #include <cstdint>
@@ -51,7 +52,7 @@ struct ConvHooks {
     // read once per process (A/B and tuning hooks of tools/conv_bench.py: one setting per run)
     int pw;         // IROCM_CONV_PW          1    conv_pw_kernel: 0 off, 1 up to 128 channels, 2 up to 256 and ahead of the one-K-step rule
     int wide;       // IROCM_CONV_WIDE        2    LDS-staged epilogue: 0 off, 1 even planes only, 2 all (9: device-side ablation)
-    int epi_probe;  // IROCM_CONV_EPI_PROBE   0    device-side ablation of the epilogue
+    int epi_probe;  // IROCM_CONV_EPI_PROBE   0    device-side ablation of the epilogue: diagnostic build only, 0 in the shipped library
     int tap;        // IROCM_CONV_TAP         1    0: the heuristic never takes the tap GEMM
     int patch;      // IROCM_CONV_PATCH       1    0: no patch / resident kernels
     int patch_wide; // IROCM_CONV_PATCH_WIDE  -1   0 / 1 force the 4-wave / 8-wave patch kernel
@@ -67,7 +68,8 @@ struct ConvHooks {
     bool conv32_pw_batched; // IROCM_CONV32_PW_BATCHED  set (to anything): fp32 unit-stride pointwise layers as one GEMM per image
 };
 inline ConvHooks conv_hooks() {
-    static const ConvHooks once = {env_int("IROCM_CONV_PW", 1),    env_int("IROCM_CONV_WIDE", 2),        env_int("IROCM_CONV_EPI_PROBE", 0),
+    static const char *const probe = diag_getenv("IROCM_CONV_EPI_PROBE"); // (diagnostic build only: diag.h; 2 = no global stores)
+    static const ConvHooks once = {env_int("IROCM_CONV_PW", 1),    env_int("IROCM_CONV_WIDE", 2),        probe ? atoi(probe) : 0,
                                    env_int("IROCM_CONV_TAP", 1),   env_int("IROCM_CONV_PATCH", 1),       env_int("IROCM_CONV_PATCH_WIDE", -1),
                                    env_int("IROCM_CONV_RESIDENT", 1), env_int("IROCM_CONV_CFG", 0),      env_int("IROCM_CONV_RES_NT4", 1),
                                    0, 0, 0, 0, 0, false};

@@ -23,6 +23,7 @@
 // plain order those four rows cover only two of the four 64-byte bank quarters (a 2-way conflict on every read: + 4 cycles). M/N-major
 // operand: gemm256_common.h's image [32 k][512 B] with the mn_f XOR, read by ds_read_b64_tr_b16 pairs.
 #include "gemm256_common.h"
+#include "diag.h"
 
 namespace irocm {
 namespace g128w {
@@ -406,7 +407,7 @@ template <typename Tr> static int launch_t(infiniRocmRuntime_t rt, GemmArgs p, b
     p.tiles_n = p.n / 256;
     w.g = p;
     w.total_tiles = p.tiles_m * p.tiles_n * p.batch;
-    const char *dbg = getenv("IROCM_W128_DBG");
+    const char *dbg = diag_getenv("IROCM_W128_DBG"); // (diagnostic build only: diag.h)
     w.dbg = dbg ? atoi(dbg) : 0;
     const unsigned grid = (unsigned)(w.total_tiles < rt->num_cu ? w.total_tiles : rt->num_cu);
     return with_layout(akm, bkm, [&](auto ak, auto bk) -> int {

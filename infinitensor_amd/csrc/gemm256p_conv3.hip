@@ -4,17 +4,21 @@
 #include "gemm256p_kernel.h"
 #include "conv_internal.h"
 #include "gemm_route.h" // persist_pick_nt
+#include "diag.h"
 
 namespace irocm {
 namespace g256p {
 
 int launch_gemm256p_conv3(infiniRocmRuntime_t rt, int dtype, const GemmArgs &p, int nt, int split, char *slab, size_t slab_bytes) {
     // timeline build (tools/conv_tap_timeline.py): IROCM_CONV_TAP_TRACE = device address (hex) of [grid][8][128] uint64 stamps
-    if (const char *tr = getenv("IROCM_CONV_TAP_TRACE")) {
+    // (diagnostic build only: the shipped library has no trace instantiation)
+#ifdef IROCM_DIAG
+    if (const char *tr = diag_getenv("IROCM_CONV_TAP_TRACE")) {
         unsigned long long *trace = (unsigned long long *)strtoull(tr, nullptr, 16);
         if (trace && dtype == INFINI_DT_F16 && nt == 4)
             return launch_p_conv<F16Traits, 4, false, true, true>(rt, p, split, slab, slab_bytes, rt->sync_flags, trace);
     }
+#endif
     if (split > 1) // (the split form exists for 256-column tiles: it is chosen when the 256 x 256 tiles alone cannot fill the chip)
         return dtype == INFINI_DT_BF16 ? launch_p_conv<Bf16Traits, 4, false, true>(rt, p, split, slab, slab_bytes, rt->sync_flags)
                                        : launch_p_conv<F16Traits, 4, false, true>(rt, p, split, slab, slab_bytes, rt->sync_flags);

@@ -21,6 +21,7 @@
 // swapped (D = B^T-fragment x A-fragment) so that a lane ends up with 4 consecutive n of one m row: 16-byte stores.
 #include "gemm_common.h"
 #include "conv_internal.h"
+#include "diag.h"
 #include <type_traits>
 
 namespace irocm {
@@ -734,7 +735,9 @@ int launch_conv_igemm32(infiniRocmRuntime_t rt, const void *x, const void *w, co
     const size_t lds = 4 * (size_t)bm * f32k::BK * 4;
     p.trace = nullptr;
     // timeline build (tools/conv32_timeline.py): IROCM_CONV32_TRACE = device address (hex) of [grid][4][128] uint64 stamps; 64 x 64 tap-major form
-    if (const char *tr = getenv("IROCM_CONV32_TRACE")) {
+    // (diagnostic build only: the shipped library has no trace instantiation)
+#ifdef IROCM_DIAG
+    if (const char *tr = diag_getenv("IROCM_CONV32_TRACE")) {
         p.trace = (unsigned long long *)strtoull(tr, nullptr, 16);
         if (p.trace && small && tm) {
             auto kern = f32k::conv_igemm32<1, true, true>;
@@ -745,6 +748,7 @@ int launch_conv_igemm32(infiniRocmRuntime_t rt, const void *x, const void *w, co
             return INFINI_ROCM_OK; // (timing only: a split launch's reduce pass is not run)
         }
     }
+#endif
 #define IROCM_C32(T_, TM_)                                                                         \
     do {                                                                                           \
         auto kern = f32k::conv_igemm32<T_, TM_>;                                                   \

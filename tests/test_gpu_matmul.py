@@ -168,6 +168,38 @@ def test_wave128_gemm_routing_and_fallback(rt):
         ops.set_matmul_variant(rt, -1)
 
 
+def test_wave128_gemm_ignores_the_diagnostic_switch(rt, monkeypatch):
+    """IROCM_W128_DBG is a hook of the diagnostic build (csrc/diag.h): bit 1 drops every C store, bit 2 makes every LDS-DMA piece read
+    the tile corner. The shipped library must not read it: the same launch with IROCM_W128_DBG=3 in the environment (the launcher would
+    read it per launch) gives the same bits as without, into an output pre-filled with a sentinel, within the per-element bound above.
+    Two tiles, two k-steps of 128: the smallest problem of the kernel's contract with more than one of each."""
+    m, n, k = 512, 256, 256
+    rng = np.random.default_rng(128)
+    a = rng.standard_normal((m, k)).astype(np.float32)
+    b = rng.standard_normal((k, n)).astype(np.float32)
+    da, db = dev(a, torch.bfloat16), dev(b, torch.bfloat16)
+    got = []
+    ops.set_matmul_variant(rt, ops.matmul_variants().index("wave128"))
+    try:
+        for dbg in (None, "3"):
+            if dbg is not None:
+                monkeypatch.setenv("IROCM_W128_DBG", dbg)
+            out = torch.full((m, n), -777.0, device="cuda", dtype=torch.bfloat16)
+            ops.matmul(rt, da, db, out=out)
+            assert ops.matmul_last_variant(rt) == "wave128"
+            rt.sync()
+            got.append(out.clone())
+    finally:
+        ops.set_matmul_variant(rt, -1)
+    assert torch.equal(got[0].view(torch.int16), got[1].view(torch.int16)), "IROCM_W128_DBG changed the result of the shipped library"
+    ar, br = R.round_to(a, "bf16"), R.round_to(b, "bf16")
+    want = R.matmul(ar, br, None, False, False)
+    bound = 2 ** -7 * np.abs(want) + 2.0 ** -17 * R.matmul(np.abs(ar), np.abs(br), None, False, False)
+    for c in got:
+        err = np.abs(host(c) - want)
+        assert (err <= bound).all(), f"max err {err.max()} at {np.unravel_index(err.argmax(), err.shape)}"
+
+
 @pytest.mark.parametrize("variant", [4, 5, 6])
 @pytest.mark.parametrize("ta,tb", [(False, False), (False, True), (True, False)])
 @pytest.mark.parametrize("shape", [(1, 16384, 1536, 192), (1, 8192, 4096, 64), (1, 4104, 3080, 128), (3, 2048, 2560, 256),

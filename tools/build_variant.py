@@ -2,7 +2,7 @@
 """Build a VARIANT of libinfini_rocm.so for same-box A/B runs: the named translation units recompiled with extra -D flags, every other
 object taken from the regular build (run `python __graft_entry__.py` first), linked to infinitensor_amd/lib/ab/<name>.so. Select it
 with INFINI_ROCM_LIB=<path> (infinitensor_amd/_lib.py).
-usage: tools/build_variant.py NAME --tus gemm256p_nt4.hip[,more.hip] -DIROCM_KV=2 [-D...]"""
+usage: tools/build_variant.py NAME --tus gemm128w.hip[,more.hip] -DIROCM_DIAG [-D...]   (the diagnostic build: tools/diag_build.py)"""
 import argparse
 import sys
 from pathlib import Path

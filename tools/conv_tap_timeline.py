@@ -8,6 +8,9 @@ import sys
 from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+from tools.diag_build import use_diag_build
+
+use_diag_build()  # (the trace hook and its kernel exist in the diagnostic build only)
 import numpy as np
 import torch
 

@@ -2,13 +2,20 @@
 rounded operands on small whole-tile shapes in all four layouts, then TFLOP/s of both kernels interleaved on the large shapes.
   python tools/gemm_wave128.py [--reps 20] [--no-check] [--ab] [--clock]
 --ab: the routing evidence (profiles/r06_gemm_wave128_ab.txt) — shipped heuristic against the forced four-wave kernel, eight interleaved
-rounds of 30 launches per shape, min / median / max. --clock (run with IROCM_W128_DBG=8): the core clock the K loops ran at."""
+rounds of 30 launches per shape, min / median / max. --clock: the core clock the K loops ran at (IROCM_W128_DBG=8, which only the
+diagnostic build reads: tools/diag_build.py; the tool builds, selects and sets both itself)."""
 import argparse
 import json
+import os
 import sys
 from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+if "--clock" in sys.argv:  # (before the package is imported: it binds the library named by INFINI_ROCM_LIB)
+    from tools.diag_build import use_diag_build
+
+    use_diag_build()
+    os.environ["IROCM_W128_DBG"] = "8"
 import torch
 
 from infinitensor_amd import RocmRuntime, ops
@@ -116,10 +123,6 @@ if __name__ == "__main__":
     rt = RocmRuntime(0)
     w = ops.matmul_variants().index("wave128")
     if a.clock:
-        import os
-
-        if os.environ.get("IROCM_W128_DBG") != "8":
-            sys.exit("run with IROCM_W128_DBG=8")
         for rep in range(3):
             for (m, n, k, ta, tb) in [(4096, 4096, 4096, False, False), (4096, 4096, 4096, True, False), (8192, 8192, 8192, False, False)]:
                 print(json.dumps(clock(rt, w, m, n, k, ta, tb)), flush=True)

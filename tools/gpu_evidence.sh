@@ -39,7 +39,7 @@ timeout -k 10 200 python tools/conv_bench.py --variants=-1,2 --res --layers 3,7,
 timeout -k 10 300 python tools/gemm_shapes.py 2>&1 | clean > $O/${R}_gemm_shapes_bf16.txt
 timeout -k 10 200 python tools/gemm_ktile_ledger.py 2>&1 | clean > $O/${R}_gemm_ktile_ledger.txt
 timeout -k 10 500 python tools/gemm_wave128.py --ab 2>&1 | clean > $O/${R}_gemm_wave128_ab.txt
-IROCM_W128_DBG=8 timeout -k 10 200 python tools/gemm_wave128.py --clock 2>&1 | clean > $O/${R}_gemm_wave128_clock.txt
+timeout -k 10 200 python tools/gemm_wave128.py --clock 2>&1 | clean > $O/${R}_gemm_wave128_clock.txt
 step "models + sweeps"
 # 5. kernel traces of the graphs and of the headline command
 rm -rf gpurun_out/prof_models; timeout -k 10 700 bash tools/profile_models.sh > $O/prof_models.log 2>&1

@@ -1,15 +1,26 @@
 #!/bin/bash
-# rocprofv3 PMC passes of the headline GEMM (separate runs; never combined with --sys-trace etc.).
+# rocprofv3 PMC passes of the headline GEMM (separate runs; never combined with --sys-trace etc.). Each pass runs under a time limit
+# and the script stops at the first pass that does not return 0.
 cd /tmp && export TMPDIR=/tmp
 REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/prof_gemm
 rm -rf $OUT; mkdir -p $OUT
 V=${1:-2}
+# One pass = interpreter and runtime start-up + 5 launches of a 4096^3 GEMM (~0.1 ms each) under rocprofv3: start-up dominates, 2-3 s
+# measured per pass with warm file caches. 60 s leaves a cold start twenty times that and still ends a hung pass within the minute.
+PASS_LIMIT=60
 for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_INSTS_LDS SQ_ACTIVE_INST_LDS" \
            "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM SQ_INST_CYCLES_VMEM" \
            "GRBM_GUI_ACTIVE" "FETCH_SIZE" "WRITE_SIZE"; do
   name=$(echo $set | tr ' ' '_' | cut -c1-40)
-  rocprofv3 --kernel-trace --pmc $set --output-format csv -d $OUT/pmc_$name -o pmc -- python $REPO/tools/run_gemm.py 4096 $V 0 5 > $OUT/pmc_$name.log 2>&1
+  t0=$(date +%s)
+  timeout -k 10 $PASS_LIMIT rocprofv3 --kernel-trace --pmc $set --output-format csv -d $OUT/pmc_$name -o pmc -- python $REPO/tools/run_gemm.py 4096 $V 0 5 > $OUT/pmc_$name.log 2>&1
+  st=$?
+  echo "pass $name: exit $st after $(( $(date +%s) - t0 )) s"
+  if [ $st -ne 0 ]; then # a pass that failed, faulted or hung: nothing more is started on this GPU
+    echo "profile_gemm: pass $name ended with status $st ($OUT/pmc_$name.log); stopping" >&2
+    exit $st
+  fi
 done
 python3 - <<PY
 import csv, glob, collections
