@@ -15,7 +15,15 @@
 //   * inside a group of eight MFMAs (accumulator row i): A reads behind MFMA 0 / 1, B reads behind MFMA 2 / 3, s_add m0 behind MFMA 4,
 //     the piece behind MFMA 6 — inline asm throughout, accumulators pinned to AGPRs ("+a"), fragments to VGPRs;
 //   * persistent over tiles (XCD-chunked, 4-row groups), the k-step stream runs THROUGH tile boundaries: the last three steps of a tile
-//     request the next tile's first three, the epilogue (permlane16 swap -> 16-byte stores) runs under them.
+//     request the next tile's first three, the epilogue (permlane16 swap -> 16-byte stores) runs under them;
+//   * a workgroup's LAST tile ends differently (final_block below): its last three k-steps request nothing and run ROW-major, so
+//     that accumulator row I is final after 24 (I + 1) MFMAs and its reads, converts, swaps and stores ride in the gaps of row
+//     I + 1's MFMAs. Why: the stamps of the diagnostic build (tools/gemm_tail_ledger.py, profiles/gemm128w_tail_ledger.txt; bf16 NN
+//     4096^3, one tile per CU, median workgroup) put 5.5 us between the last MFMA and the end of the workgroup — 5.0 of them ISSUING
+//     the 32 stores of a wave, i.e. waiting for the store path: 32 MiB leave 256 CUs at once, at what memory takes — and no byte of C
+//     moved before them. With the final block the same stretch is 1.0 us; the K phase grows by 3.1 us (the stores now stall issue
+//     between MFMAs), the workgroup ends 1.5 us earlier. The C stores are write-through (sc0 sc1): a row's bytes start for memory
+//     when they are stored, not at the end-of-kernel write-back — alone worth 2.0 us of 91 (profiles/gemm128w_final_block_ab.txt).
 // LDS images. K-major operand (k contiguous in memory): 16-row blocks of sixteen 64-byte SLOTS; row l15 of a block sits in slot
 // s = b0 | b3 << 1 | (b2 b1) << 2 of its bits and physical 16-byte chunk c' of slot s holds logical chunk c' ^ (s >> 2). The bit
 // permutation is what makes ds_read_b128 conflict-free: the counters (SQ_LDS_BANK_CONFLICT) showed that a b128 read is served in four
@@ -38,27 +46,36 @@ constexpr int kGroupM = 4;       // tile rows per group: 32 consecutive tile ind
 struct WArgs {
     GemmArgs g;
     int total_tiles;
-    int dbg; // IROCM_W128_DBG (bring-up / diagnosis): 1 = no stores, 2 = every piece reads the tile corner, 8 = clock stamps into C[0..15]
+    int dbg; // IROCM_W128_DBG (bring-up / diagnosis): 1 = no stores (but those the final block issues under its MFMAs), 2 = every piece reads the tile corner, 8 = K-loop clocks into C[0..15], 16 = clock stamps into `stamps`
+    unsigned long long *stamps; // dbg & 16 (diagnostic build only): kStamps values per workgroup in the runtime workspace, never in C
 };
+#ifdef IROCM_DIAG
+constexpr bool kDiag = true;
+#else
+constexpr bool kDiag = false; // the shipped kernels hold no clock read
+#endif
+constexpr int kStamps = 8; // core clock at entry, first MFMA, last MFMA, last store issued, after the final wait; 100 MHz clock at entry,
+                           // last MFMA, after the final wait (tools/gemm_tail_ledger.py)
 
-// Fragment sets: two register sets x 8 fragments of one operand.
+// Fragment sets: two register sets x 8 fragments of one operand (a third, and DST = a register other than the fragment's own, only in
+// the final block of a workgroup's last tile: registers are assigned by liveness, a set nobody holds costs none).
 template <bool KMAJOR> struct Frags;
 template <> struct Frags<true> {
-    s16x8_t v[2][8];
+    s16x8_t v[3][8];
     unsigned base[2]; // lane address in stage 0 / stage 2 (stages 1 / 3 by the immediate offset)
     __device__ __forceinline__ void init(unsigned lds_oper, int half, int l15, int g4) {
         const int slot = (l15 & 1) | (((l15 >> 3) & 1) << 1) | (((l15 >> 1) & 3) << 2); // row l15 of a 16-row block -> its 64-byte slot
         base[0] = lds_oper + (unsigned)(half * 8192 + slot * 64 + ((g4 ^ (slot >> 2)) & 3) * 16);
         base[1] = base[0] + 2u * kStage;
     }
-    template <int SET, int F, int STAGE> __device__ __forceinline__ void read0() {
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v[SET][F]) : "v"(base[STAGE >> 1]), "i"(F * 1024 + (STAGE & 1) * kStage));
+    template <int SET, int F, int STAGE, int DST = F> __device__ __forceinline__ void read0() {
+        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v[SET][DST]) : "v"(base[STAGE >> 1]), "i"(F * 1024 + (STAGE & 1) * kStage));
     }
-    template <int SET, int F, int STAGE> __device__ __forceinline__ void read1() {}
+    template <int SET, int F, int STAGE, int DST = F> __device__ __forceinline__ void read1() {}
     template <int SET, int F> __device__ __forceinline__ s16x8_t get() const { return v[SET][F]; }
 };
 template <> struct Frags<false> {
-    s16x4_t lo[2][8], hi[2][8];
+    s16x4_t lo[3][8], hi[3][8];
     unsigned addr[8]; // lane address of fragment f in stage 0 (stage 1 by the immediate offset, stages 2 / 3 by one VALU add at the read:
                       // sixteen more address registers per operand spilled the both-operands-M/N-major build)
     __device__ __forceinline__ void init(unsigned lds_oper, int half, int l15, int g4) {
@@ -70,13 +87,13 @@ template <> struct Frags<false> {
             addr[f] = lds_oper + mn_lane + (unsigned)c16 * 16u;
         }
     }
-    template <int SET, int F, int STAGE> __device__ __forceinline__ void read0() {
+    template <int SET, int F, int STAGE, int DST = F> __device__ __forceinline__ void read0() {
         const unsigned a = STAGE >= 2 ? addr[F] + 2u * kStage : addr[F];
-        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(lo[SET][F]) : "v"(a), "i"((STAGE & 1) * kStage));
+        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(lo[SET][DST]) : "v"(a), "i"((STAGE & 1) * kStage));
     }
-    template <int SET, int F, int STAGE> __device__ __forceinline__ void read1() {
+    template <int SET, int F, int STAGE, int DST = F> __device__ __forceinline__ void read1() {
         const unsigned a = STAGE >= 2 ? addr[F] + 2u * kStage : addr[F];
-        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(hi[SET][F]) : "v"(a), "i"((STAGE & 1) * kStage + 2048));
+        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(hi[SET][DST]) : "v"(a), "i"((STAGE & 1) * kStage + 2048));
     }
     template <int SET, int F> __device__ __forceinline__ s16x8_t get() const {
         return s16x8_t{lo[SET][F][0], lo[SET][F][1], lo[SET][F][2], lo[SET][F][3], hi[SET][F][0], hi[SET][F][1], hi[SET][F][2], hi[SET][F][3]};
@@ -130,6 +147,40 @@ constexpr int slot_piece(int n, int I, int slot) {
     return slot == 0 ? I : (8 + I < n ? 8 + I : -1);
 }
 
+// The final block's epilogue of one accumulator row as 60 single instructions, in the order they are issued one to three per MFMA gap
+// of the NEXT row: P(jp) = the 8 accumulator reads and 4 packed converts of column-tile pair jp (read, read, convert; 12), W(jp) = its
+// two lane-group swaps, T(jp) = its 16-byte store. Order P0 P1 W0 P2 T0 W1 P3 T1 W2 T2 W3 T3: at least four instructions lie between a
+// convert and the swap that reads it (the hazard asks for two wait states), and a store's registers are rewritten by the next row only.
+// (the instruction Tr::pack2 compiles to, as a statement that stays where it is written)
+template <typename Tr> __device__ __forceinline__ unsigned cvt_pk_a(float lo, float hi) {
+    unsigned r;
+    if constexpr (Tr::kDType == INFINI_DT_BF16) asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
+    else asm volatile("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
+    return r;
+}
+// C stores write through (tools/build_variant.py ... -DIROCM_W128_C_WB builds the write-back variant the A/B was taken against)
+#ifdef IROCM_W128_C_WB
+#define W128_ST_MOD ""
+#else
+#define W128_ST_MOD " sc0 sc1"
+#endif
+struct EpiUnit {
+    int kind, jp, t; // kind 0 = P (t = 0 .. 11), 1 = W (t = 0, 1), 2 = T
+};
+constexpr int kEpiUnits = 60;
+constexpr EpiUnit epi_unit(int e) {
+    const int kind[12] = {0, 0, 1, 0, 2, 1, 0, 2, 1, 2, 1, 2};
+    const int jp[12] = {0, 1, 0, 2, 0, 1, 3, 1, 2, 2, 3, 3};
+    const int size[12] = {12, 12, 2, 12, 1, 2, 12, 1, 2, 1, 2, 1};
+    int s = 0;
+    for (int i = 0; i < 12; ++i) {
+        if (e < s + size[i])
+            return {kind[i], jp[i], e - s};
+        s += size[i];
+    }
+    return {-1, 0, 0};
+}
+
 template <typename Tr, bool FIRST> __device__ __forceinline__ void mfma_a(f32x4 &acc, s16x8_t x, s16x8_t y) {
     if constexpr (Tr::kDType == INFINI_DT_BF16) {
         if constexpr (FIRST) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=a"(acc) : "v"(x), "v"(y));
@@ -144,6 +195,11 @@ template <typename Tr, bool AKM, bool BKM>
 __global__ __launch_bounds__(256, 1) void gemm128w_kernel(WArgs pw) {
     extern __shared__ __attribute__((aligned(1024))) char smem[];
     const GemmArgs &p = pw.g;
+    unsigned long long tc0 = 0, tr0 = 0; // kernel entry
+    if constexpr (kDiag) {
+        tc0 = __builtin_amdgcn_s_memtime();
+        tr0 = __builtin_amdgcn_s_memrealtime();
+    }
     const int t = threadIdx.x, lane = t & 63, l15 = lane & 15, g4 = lane >> 4;
     int w;
     asm volatile("v_readfirstlane_b32 %0, %1" : "=s"(w) : "v"(t >> 6));
@@ -286,7 +342,7 @@ __global__ __launch_bounds__(256, 1) void gemm128w_kernel(WArgs pw) {
     __builtin_amdgcn_s_barrier();
 
     // one k-step: S = position in the block of four (register set S & 1; reads stage S + 1; its pieces go to stage S + 3)
-    const char *na = pa, *nb = pb; // the next tile's corner (this tile's when there is none: requested, never read)
+    const char *na = pa, *nb = pb; // the next tile's corner
     auto step = [&](auto sc, auto firstc, bool last_block) __attribute__((always_inline)) {
         constexpr int S = decltype(sc)::value;
         constexpr bool FIRST = decltype(firstc)::value;
@@ -330,34 +386,125 @@ __global__ __launch_bounds__(256, 1) void gemm128w_kernel(WArgs pw) {
         asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NP) : "memory");
         __builtin_amdgcn_s_barrier();
     };
-
-    const unsigned long long tc0 = __builtin_amdgcn_s_memtime(), tr0 = __builtin_amdgcn_s_memrealtime();
+    constexpr std::integral_constant<int, 0> k0{};
+    constexpr std::integral_constant<int, 1> k1{};
+    constexpr std::integral_constant<int, 2> k2{};
+    constexpr std::integral_constant<int, 3> k3{};
+    auto block = [&](auto firstc, bool last_block) __attribute__((always_inline)) { // four k-steps
+        step(k0, firstc, last_block);
+        step(k1, std::false_type{}, last_block);
+        step(k2, std::false_type{}, last_block);
+        step(k3, std::false_type{}, last_block);
+    };
+    // (clock stamps: the diagnostic build only, workgroup-uniform scalars until wave 0 stores them behind the final wait)
+    unsigned long long tc_first = 0, tr_first = 0, tc_mfma = 0, tr_mfma = 0, tc_store = 0;
+    if constexpr (kDiag) {
+        tc_first = __builtin_amdgcn_s_memtime();
+        tr_first = __builtin_amdgcn_s_memrealtime();
+    }
     const unsigned total = (unsigned)pw.total_tiles;
     const long ldc2 = (long)p.n * 2;
-    for (; tile < total; tile += grid) {
-        {
-            const unsigned nt = tile + grid < total ? tile + grid : tile;
-            long dummy;
-            decode(nt, na, nb, dummy);
-            na = uniform(na);
-            nb = uniform(nb);
-        }
-        {
-            const bool last = nkb == 1;
-            step(std::integral_constant<int, 0>{}, std::true_type{}, last);
-            step(std::integral_constant<int, 1>{}, std::false_type{}, last);
-            step(std::integral_constant<int, 2>{}, std::false_type{}, last);
-            step(std::integral_constant<int, 3>{}, std::false_type{}, last);
-        }
-        for (int kb = 1; kb < nkb; ++kb) {
-            const bool last = kb == nkb - 1;
-            step(std::integral_constant<int, 0>{}, std::false_type{}, last);
-            step(std::integral_constant<int, 1>{}, std::false_type{}, last);
-            step(std::integral_constant<int, 2>{}, std::false_type{}, last);
-            step(std::integral_constant<int, 3>{}, std::false_type{}, last);
+    // ---- the final block: k-steps L-3 .. L-1 of a workgroup's LAST tile, behind step 0 of its last block (which requested the last
+    // M/N-major pieces and read k-step L-3's fragments into set 1). No requests are left and no next tile, so the order turns ROW-major:
+    // for accumulator row I the 3 x 8 MFMAs of k-steps L-3, L-2, L-1 (ascending k into the same accumulator: the sums are the k-outer
+    // order's, bit for bit), after which row I is final — and its epilogue (epi_unit: 32 reads, 16 converts, 8 swaps, 4 stores) is issued
+    // two or three instructions per gap between row I + 1's 24 MFMAs, so that C leaves the CU while the matrix pipe still works; row 7's
+    // stays exposed. Fragments: B of all three k-steps (set 1 as read; L-2 -> set 0 and L-1 -> set 2, read under row 0's first sixteen
+    // MFMAs), A of k-step L-3 as read (set 1), A of L-2 / L-1 per row into slots (I & 1) * 2 + {0, 1} of set 0, read under row I - 1's
+    // last eight MFMAs. Row 0 holds the two waits that have no distance: for everything in flight plus the one barrier in front of the
+    // first read of stage 3, and for B of k-step L-1 in front of its first use; behind the barrier nothing writes LDS any more.
+    auto final_block = [&]() __attribute__((always_inline)) {
+        const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+        const unsigned c_lane = (unsigned)(((long)(ln & 15) * p.n + ((ln >> 4) & 1) * 16 + (ln >> 5) * 8) * 2);
+        char *cw = (char *)p.c + (c_elem + (long)wr * 128 * p.n + wc * 128) * 2;
+        cw = (char *)uniform(cw);
+        unsigned pu[8], pv[8]; // the retiring row's packed halves (epilogue below: u / v)
+        float t0 = 0.f, t1 = 0.f;
+        sfor<8>([&](auto ic) {
+            constexpr int I = decltype(ic)::value;
+            constexpr int SA = (I & 1) * 2, SN = ((I + 1) & 1) * 2; // this row's / the next row's A slots in set 0
+            char *cb = cw + (long)(I > 0 ? I - 1 : 0) * 16 * ldc2; // the retiring row's base: pinned here, first read five MFMAs on
+            asm volatile("" : "+s"(cb));
+            if constexpr (I > 0) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // this row's A slots, read six gaps ago
+            sfor<24>([&](auto mc) {
+                constexpr int M = decltype(mc)::value, KS = M >> 3, J = M & 7;
+                if constexpr (I == 0 && M == 8) {
+                    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+                    __builtin_amdgcn_s_barrier();
+                }
+                if constexpr (I == 0 && M == 16) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                if constexpr (KS == 0) mfma_a<Tr, false>(acc[I][J], fb.template get<1, J>(), fa.template get<1, I>());
+                if constexpr (KS == 1) mfma_a<Tr, false>(acc[I][J], fb.template get<0, J>(), fa.template get<0, SA>());
+                if constexpr (KS == 2) mfma_a<Tr, false>(acc[I][J], fb.template get<2, J>(), fa.template get<0, SA + 1>());
+                if constexpr (I == 0 && KS == 0) {
+                    fb.template read0<0, J, 2>();
+                    fb.template read1<0, J, 2>();
+                    if constexpr (J == 0) {
+                        fa.template read0<0, 0, 2, 0>();
+                        fa.template read1<0, 0, 2, 0>();
+                    }
+                }
+                if constexpr (I == 0 && KS == 1) {
+                    fb.template read0<2, J, 3>();
+                    fb.template read1<2, J, 3>();
+                    if constexpr (J == 0) {
+                        fa.template read0<0, 0, 3, 1>();
+                        fa.template read1<0, 0, 3, 1>();
+                    }
+                }
+                if constexpr (I < 7 && M == 16) {
+                    fa.template read0<0, I + 1, 2, SN>();
+                    fa.template read1<0, I + 1, 2, SN>();
+                }
+                if constexpr (I < 7 && M == 17) {
+                    fa.template read0<0, I + 1, 3, SN + 1>();
+                    fa.template read1<0, I + 1, 3, SN + 1>();
+                }
+                if constexpr (I > 0) {
+                    constexpr int R = I - 1, E0 = M * kEpiUnits / 24, E1 = (M + 1) * kEpiUnits / 24;
+                    sfor<E1 - E0>([&](auto uc) {
+                        constexpr EpiUnit un = epi_unit(E0 + decltype(uc)::value);
+                        if constexpr (un.kind == 0) {
+                            constexpr int Q = 2 * un.jp + un.t / 6, H = (un.t % 6) / 3, RR = un.t % 3;
+                            if constexpr (RR < 2) {
+                                const float src = acc[R][Q][2 * H + RR];
+                                float dst;
+                                asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(dst) : "a"(src));
+                                if constexpr (RR == 0) t0 = dst;
+                                else t1 = dst;
+                            } else if constexpr (un.t < 6) {
+                                pu[2 * un.jp + H] = cvt_pk_a<Tr>(t0, t1);
+                            } else {
+                                pv[2 * un.jp + H] = cvt_pk_a<Tr>(t0, t1);
+                            }
+                        } else if constexpr (un.kind == 1) {
+                            unsigned x = pu[2 * un.jp + un.t], y = pv[2 * un.jp + un.t];
+                            asm volatile("v_permlane16_swap_b32 %0, %1" : "+v"(x), "+v"(y));
+                            pu[2 * un.jp + un.t] = x;
+                            pv[2 * un.jp + un.t] = y;
+                        } else {
+                            const u32x4_t d = u32x4_t{pu[2 * un.jp], pu[2 * un.jp + 1], pv[2 * un.jp], pv[2 * un.jp + 1]};
+                            const unsigned cl = c_lane;
+                            char *cbs = cb;
+                            asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3" W128_ST_MOD ::"v"(cl), "v"(d), "s"(cbs), "i"(un.jp * 64) : "memory");
+                        }
+                    });
+                }
+            });
+        });
+    };
+    auto epilogue = [&](auto firstrowc) __attribute__((always_inline)) { // rows FIRSTROW .. 7 (the final block leaves row 7 only)
+        constexpr int FIRSTROW = decltype(firstrowc)::value;
+        if constexpr (kDiag) {
+            tc_mfma = __builtin_amdgcn_s_memtime();
+            tr_mfma = __builtin_amdgcn_s_memrealtime();
         }
         // ---- epilogue: lane l holds, of tile (i, j), row l15 and the four columns g4 * 4 ...; a permlane16 swap between the packed
-        // halves of tiles j and j + 1 leaves every lane eight consecutive columns: one 16-byte store per tile pair ------------------
+        // halves of tiles j and j + 1 leaves every lane eight consecutive columns: one 16-byte store per tile pair. Per accumulator row
+        // in BATCHES — the row's 32 reads and 16 converts (the compiler's), then its 8 swaps, then its 4 stores, each batch ONE asm
+        // statement — so that distance keeps the hazards a pad kept per instruction before: the only pads left are the two wait states
+        // in front of a row's first swap (the compiler orders the converts and may put the one a swap reads right in front of the
+        // statement) and behind its last store (the next row's first convert may write that store's data registers) -------------------
         asm volatile("s_nop 15\n\ts_nop 15" ::: "memory"); // the last MFMAs' results (inline asm: no hazard bookkeeping by the compiler)
         // (the lane's store offset is rebuilt from mbcnt here: carried across the K loop it is the register the M/N x M/N build spills)
         const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
@@ -367,37 +514,77 @@ __global__ __launch_bounds__(256, 1) void gemm128w_kernel(WArgs pw) {
         if (!(pw.dbg & 1))
         sfor<8>([&](auto ic) {
             constexpr int I = decltype(ic)::value;
-            char *ci = cw + (long)I * 16 * ldc2;
-            sfor<4>([&](auto jpc) {
-                constexpr int JP = decltype(jpc)::value;
-                const f32x4 x = acc[I][2 * JP], y = acc[I][2 * JP + 1];
-                unsigned u0 = Tr::pack2(x[0], x[1]), u1 = Tr::pack2(x[2], x[3]);
-                unsigned v0 = Tr::pack2(y[0], y[1]), v1 = Tr::pack2(y[2], y[3]);
-                asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(u0), "+v"(v0));
-                asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(u1), "+v"(v1));
-                // (asm: a store the compiler knows about makes it guard the tile loop with s_waitcnt vmcnt(0), i.e. wait out the next
-                // tile's pieces; a store has read its registers once it has issued)
-                const u32x4_t d = u32x4_t{u0, u1, v0, v1};
-                const unsigned cl = c_lane; // (copies: clang does not capture a variable a generic lambda names only in an asm operand)
-                char *cb = ci;
-                if constexpr (JP == 0) asm volatile("s_nop 4" : "+s"(cb)); // (the row block's base was just computed by SALU)
-                // (s_nop: a store of more than 64 bits must be two wait states ahead of a VALU write of its data registers — a rule
-                // the compiler keeps only for stores it knows)
-                asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3\n\ts_nop 1" ::"v"(cl), "v"(d), "s"(cb), "i"(JP * 64) : "memory");
-            });
+            if constexpr (I < FIRSTROW) return;
+            char *cb = cw + (long)I * 16 * ldc2;
+            asm volatile("s_nop 4" : "+s"(cb)); // (the row block's base was just computed by SALU: five wait states ahead of a VMEM read)
+            unsigned u[8], v[8]; // packed halves of tiles 2 JP (u) and 2 JP + 1 (v): columns 0 1 | 2 3 of the lane's four
+#pragma unroll
+            for (int jp = 0; jp < 4; ++jp) {
+                const f32x4 x = acc[I][2 * jp], y = acc[I][2 * jp + 1];
+                u[2 * jp] = Tr::pack2(x[0], x[1]);
+                u[2 * jp + 1] = Tr::pack2(x[2], x[3]);
+                v[2 * jp] = Tr::pack2(y[0], y[1]);
+                v[2 * jp + 1] = Tr::pack2(y[2], y[3]);
+            }
+            asm volatile("s_nop 1\n\t"
+                         "v_permlane16_swap_b32 %0, %8\n\tv_permlane16_swap_b32 %1, %9\n\tv_permlane16_swap_b32 %2, %10\n\t"
+                         "v_permlane16_swap_b32 %3, %11\n\tv_permlane16_swap_b32 %4, %12\n\tv_permlane16_swap_b32 %5, %13\n\t"
+                         "v_permlane16_swap_b32 %6, %14\n\tv_permlane16_swap_b32 %7, %15"
+                         : "+v"(u[0]), "+v"(u[1]), "+v"(u[2]), "+v"(u[3]), "+v"(u[4]), "+v"(u[5]), "+v"(u[6]), "+v"(u[7]), "+v"(v[0]), "+v"(v[1]),
+                           "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]));
+            // (asm: a store the compiler knows about makes it guard the tile loop with s_waitcnt vmcnt(0), i.e. wait out the next tile's
+            // pieces; a store has read its registers once it has issued. The first store reads what swaps 0 and 1 wrote, six swaps back.)
+            const u32x4_t d0 = u32x4_t{u[0], u[1], v[0], v[1]}, d1 = u32x4_t{u[2], u[3], v[2], v[3]};
+            const u32x4_t d2 = u32x4_t{u[4], u[5], v[4], v[5]}, d3 = u32x4_t{u[6], u[7], v[6], v[7]};
+            const unsigned cl = c_lane; // (copies: clang does not capture a variable a generic lambda names only in an asm operand)
+            asm volatile("global_store_dwordx4 %0, %1, %5" W128_ST_MOD "\n\tglobal_store_dwordx4 %0, %2, %5 offset:64" W128_ST_MOD "\n\t"
+                         "global_store_dwordx4 %0, %3, %5 offset:128" W128_ST_MOD "\n\tglobal_store_dwordx4 %0, %4, %5 offset:192" W128_ST_MOD "\n\ts_nop 1" ::"v"(cl),
+                         "v"(d0), "v"(d1), "v"(d2), "v"(d3), "s"(cb)
+                         : "memory");
         });
-        // this workgroup's next tile
+        if constexpr (kDiag) tc_store = __builtin_amdgcn_s_memtime();
+    };
+    // Every tile but the workgroup's last: the k-step stream runs through into the next tile, whose first pieces stay in flight under
+    // the epilogue. The LAST tile is separate code behind the loop, not a branch inside it: the 256 accumulator registers meet at no
+    // join but the K loops' own back edges (hipcc answers a join of two inline-asm paths with hundreds of copies and spills).
+    for (; tile + grid < total; tile += grid) {
         {
-            const char *ta, *tb;
-            const unsigned nt = tile + grid < total ? tile + grid : tile;
-            decode(nt, ta, tb, c_elem);
+            long dummy;
+            decode(tile + grid, na, nb, dummy);
+            na = uniform(na);
+            nb = uniform(nb);
         }
+        block(std::true_type{}, nkb == 1);
+        for (int kb = 1; kb < nkb; ++kb) block(std::false_type{}, kb == nkb - 1);
+        epilogue(k0);
+        const char *ta, *tb;
+        decode(tile + grid, ta, tb, c_elem);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // pieces requested past the last tile
-    if ((pw.dbg & 8) && blockIdx.x == 0 && w == 0 && __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0) { // tools/gemm_wave128.py --clock: the K loops' length on the core clock and on the 100 MHz
-        unsigned long long *d = (unsigned long long *)p.c; // reference, over the first 16 bytes of C
-        d[0] = __builtin_amdgcn_s_memtime() - tc0;
-        d[1] = __builtin_amdgcn_s_memrealtime() - tr0;
+    // The last tile: step 0 of its last block requests the last M/N-major pieces, the final block behind it requests nothing.
+    if (nkb == 1) {
+        step(k0, std::true_type{}, false);
+        final_block();
+        epilogue(std::integral_constant<int, 7>{});
+    } else {
+        block(std::true_type{}, false);
+        for (int kb = 1; kb < nkb - 1; ++kb) block(std::false_type{}, false);
+        step(k0, std::false_type{}, false);
+        final_block();
+        epilogue(std::integral_constant<int, 7>{});
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the last tile's stores (and, where dbg & 1 dropped them, nothing)
+    if constexpr (kDiag) {
+        const bool lane0 = w == 0 && __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0;
+        if ((pw.dbg & 16) && lane0) { // tools/gemm_tail_ledger.py
+            unsigned long long *d = pw.stamps + (size_t)blockIdx.x * kStamps;
+            d[0] = tc0, d[1] = tc_first, d[2] = tc_mfma, d[3] = tc_store, d[4] = __builtin_amdgcn_s_memtime();
+            d[5] = tr0, d[6] = tr_mfma, d[7] = __builtin_amdgcn_s_memrealtime();
+        }
+        if ((pw.dbg & 8) && blockIdx.x == 0 && lane0) { // tools/gemm_wave128.py --clock: the K loops' length on the core clock and on the
+            unsigned long long *d = (unsigned long long *)p.c; // 100 MHz reference, over the first 16 bytes of C
+            d[0] = __builtin_amdgcn_s_memtime() - tc_first;
+            d[1] = __builtin_amdgcn_s_memrealtime() - tr_first;
+        }
     }
 }
 
@@ -409,7 +596,14 @@ template <typename Tr> static int launch_t(infiniRocmRuntime_t rt, GemmArgs p, b
     w.total_tiles = p.tiles_m * p.tiles_n * p.batch;
     const char *dbg = diag_getenv("IROCM_W128_DBG"); // (diagnostic build only: diag.h)
     w.dbg = dbg ? atoi(dbg) : 0;
+    w.stamps = nullptr;
     const unsigned grid = (unsigned)(w.total_tiles < rt->num_cu ? w.total_tiles : rt->num_cu);
+    if (w.dbg & 16) {
+        void *ws = nullptr;
+        if (int st = infini_rocm_workspace(rt, (size_t)grid * kStamps * sizeof(unsigned long long), &ws))
+            return st;
+        w.stamps = (unsigned long long *)ws;
+    }
     return with_layout(akm, bkm, [&](auto ak, auto bk) -> int {
         auto kern = gemm128w_kernel<Tr, decltype(ak)::value, decltype(bk)::value>;
         IROCM_LDS_ATTR(kern, kLds, rt);
