@@ -216,18 +216,21 @@ __global__ __launch_bounds__(256) void softmax_block_kernel(const T *__restrict_
         for (long i = t; i < n; i += 256) { // online max/sum (reference softmax.cu:8-17)
             const float v = Elem<T>::ld(xr + i);
             const float nm = fmaxf(m, v);
-            s = s * __expf(m - nm) + __expf(v - nm);
+            if (nm != -INFINITY) // a masked prefix (all -inf so far) adds nothing, and exp(m - nm) would be exp(-inf + inf) = NaN
+                s = s * __expf(m - nm) + __expf(v - nm);
             m = nm;
         }
         float gm = wave_max(m);
-        s *= __expf(m - gm);
+        if (gm != -INFINITY) // (a wave whose whole share is masked holds s = 0)
+            s *= __expf(m - gm);
         s = wave_sum(s);
         if (lane == 0)
             red[w] = gm;
         __syncthreads();
         const float bm = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
         __syncthreads();
-        s *= __expf(gm - bm);
+        if (bm != -INFINITY)
+            s *= __expf(gm - bm);
         if (lane == 0)
             red[w] = s;
         __syncthreads();
@@ -254,7 +257,8 @@ __global__ __launch_bounds__(256) void softmax_strided_kernel(const T *__restric
         for (long d = 0; d < dimsize; ++d) {
             const float v = Elem<T>::ld(xp + d * inner);
             const float nm = fmaxf(m, v);
-            s = s * __expf(m - nm) + __expf(v - nm);
+            if (nm != -INFINITY) // as in softmax_block_kernel: a masked prefix adds nothing
+                s = s * __expf(m - nm) + __expf(v - nm);
             m = nm;
         }
         const float inv = 1.0f / s;
