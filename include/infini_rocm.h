@@ -302,6 +302,16 @@ int infini_rocm_add_norm(infiniRocmRuntime_t rt, int dtype, int rms, const void 
 int infini_rocm_bias_add_norm(infiniRocmRuntime_t rt, int dtype, int rms, const void *a, const void *pre, const void *b,
                               const void *scale, const void *bias, void *y, int64_t outer, int64_t norm_size,
                               int64_t scale_size, int64_t bias_size, float eps);
+/* What the most recent softmax / layer_norm / rms_norm / add_norm / bias_add_norm call on this runtime launched ("none" before the
+ * first and for a zero extent): kernel family and template choices, e.g. "softmax_wave/C2/aligned/R2", "norm_rows/B8/C3/ADD1",
+ * "norm_blockreg/C4/ADD2", "norm_block/unaligned", "softmax_strided"; "chain" when (bias_)add_norm ran Add and the norm one after the
+ * other. The string lives in the runtime and is overwritten by the next row-op call. */
+int infini_rocm_rowop_last_route(infiniRocmRuntime_t rt, const char **route);
+/* The route such a call would take, without a runtime or a GPU (csrc/rowops_route.h: rowop_plan), written to route[cap]. op: 0 softmax,
+ * 1 layer_norm, 2 rms_norm, 3 add_norm (has_pre != 0: bias_add_norm with a row `pre`); inner is 1 for the norms; ptr_lo: the OR of the
+ * low four address bits of every pointer the call would be given (0 = all 16-byte aligned); num_cu: the device's CU count. */
+int infini_rocm_rowop_plan_route(int op, int dtype, int64_t outer, int64_t n, int64_t inner, int has_pre, int ptr_lo, int num_cu,
+                                 char *route, size_t cap);
 
 /* Fused prefill attention  O = softmax(scale * Q K^T + mask) V  per (batch x head); f16 / bf16, head dim 64 or 128.
  * Replaces the chain MatMul(Q, K^T) -> Div/Mul(scalar) -> Add(mask) -> Softmax -> MatMul(P, V) of the reference graph

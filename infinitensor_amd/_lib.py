@@ -100,6 +100,8 @@ def lib() -> C.CDLL:
     sig("infini_rocm_softmax", [vp, i32, vp, vp, i64, i64, i64])
     sig("infini_rocm_layer_norm", [vp, i32, vp, vp, vp, vp, i64, i64, i64, i64, f32])
     sig("infini_rocm_rms_norm", [vp, i32, vp, vp, vp, i64, i64, f32])
+    sig("infini_rocm_rowop_last_route", [vp, C.POINTER(C.c_char_p)])
+    sig("infini_rocm_rowop_plan_route", [i32, i32, i64, i64, i64, i32, i32, i32, C.c_char_p, sz])
     sig("infini_rocm_conv2d_set_variant", [vp, i32])
     sig("infini_rocm_conv2d_last_route", [vp, C.POINTER(C.c_char_p)])
     sig("infini_rocm_conv2d_plan_route", [i32, i64, i64, i64, i64, i64, i64, i64, i32, i32, i32, i32, i32, i32, i64, i32, i32, i32, i32,

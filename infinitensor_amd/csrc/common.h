@@ -140,6 +140,7 @@ struct infiniRocmRuntime {
     int matmul_compute_type = 0; // 0 exact fp32 products, 1 bf16, 2 fp16 (fp32 MatMul only; MatmulObj::getComputeType())
     int last_matmul_variant = -1; // the variant the most recent matmul call actually launched
     const char *last_conv_route = "none"; // which implementation the most recent conv2d call launched
+    char last_rowop_route[40] = "none"; // the route of the most recent row-op call (rowops_route.h: rowop_route_name)
     int conv_variant = -1;
     // conv weights declared constant by the caller: their re-packed images are cached (WCacheEntry) instead of rebuilt
     int conv_const_weights = 0;

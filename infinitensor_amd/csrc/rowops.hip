@@ -14,7 +14,8 @@
 // reference (softmax.cu:8-17).
 // All arithmetic is fp32 regardless of the storage dtype.
 #include "common.h"
-#include <cstdlib>
+#include "rowops_route.h"
+#include <type_traits>
 
 namespace irocm {
 
@@ -813,194 +814,124 @@ __global__ __launch_bounds__(256) void softmax_blockreg_kernel(const T *__restri
     }
 }
 
-static inline bool is_aligned16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
-static inline int env_int(const char *name, int dflt) {
-    const char *e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-// The persistent grid of ONE kernel: as many 256-thread workgroups per CU as are RESIDENT at once (asked from the HIP runtime once
+// ------------------------------------------------------------------------------------------------
+// Host part: rowop_plan (rowops_route.h) says what runs; launch_plan maps its answer to the instantiation.
+// ------------------------------------------------------------------------------------------------
+// The cap of kGridResident for ONE kernel: as many 256-thread workgroups per CU as are RESIDENT at once (asked from the HIP runtime once
 // per kernel; at most 8). With a fixed eight per CU a kernel of 86 registers (five resident) ran 5 + 3: the last three workgroups of
 // every CU started when the first five had finished all their rows — the same tail nnops.hip's short-row reduction had (0.56 -> 0.68).
-template <auto Kern> static inline unsigned pgrid_k(int64_t blocks, int num_cu) {
+template <auto Kern> static inline int64_t pgrid_k(int num_cu) {
     static const int per_cu = [] {
-        const int forced = env_int("IROCM_ROWOPS_BLOCKS_PER_CU", 0); // tuning hook
-        if (forced > 0)
-            return forced;
         int nb = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, Kern, 256, 0) != hipSuccess || nb < 1)
             nb = 8;
         return nb < 8 ? nb : 8;
     }();
-    const int64_t cap = (int64_t)num_cu * per_cu;
-    return (unsigned)(blocks < cap ? (blocks < 1 ? 1 : blocks) : cap);
+    return (int64_t)num_cu * per_cu;
 }
 
-// Launch of the fast row path (norm_rows_kernel); false when the rows do not qualify (unaligned, or > 4 KiB).
-template <typename T, bool RMS, int ADD>
-static bool launch_norm_rows(infiniRocmRuntime_t rt, const T *x, const T *x2, const T *pre, const T *scale, const T *bias, T *y,
-                             int64_t outer, int64_t n, int64_t scale_size, int64_t bias_size, float eps) {
-    constexpr int VEC = Elem<T>::VEC;
-    const int64_t row_bytes = n * (int64_t)sizeof(T);
-    const bool al = is_aligned16(x) && (!ADD || is_aligned16(x2)) && (ADD != 2 || is_aligned16(pre)) && is_aligned16(y) &&
-                    is_aligned16(scale) && (bias == nullptr || is_aligned16(bias)) && (n % VEC == 0);
-    if (!al || row_bytes > 4096 || outer == 0)
-        return false;
-    // chunk width: the one that leaves the fewest idle lanes (768 f16 = 3 x 8 B, not 2 x 16 B with half a chunk idle)
-    const int c16 = (int)ceil_div(row_bytes, (int64_t)1024), c8 = (int)ceil_div(row_bytes, (int64_t)512);
-    const bool use8 = (c8 == 1 || c8 == 3) && (c8 * 512 - row_bytes) < (c16 * 1024 - row_bytes);
-    static const int rpw_env = env_int("IROCM_NORM_RPW", 0); // tuning hook
-    static const int per_cu = env_int("IROCM_NORM_BLOCKS_PER_CU", 4); // 16 persistent waves per CU, rows pipelined
-    const int rpw = (!ADD && rpw_env == 2) ? 2 : 1;
-    const int64_t blocks = ceil_div(outer, (int64_t)4 * rpw), cap = (int64_t)rt->num_cu * per_cu;
-    const dim3 grid((unsigned)(blocks < cap ? blocks : cap));
-#define ROWS_GO(B, C, R)                                                                                        \
-    hipLaunchKernelGGL((norm_rows_kernel<T, B, C, RMS, R, ADD>), grid, dim3(256), 0, rt->stream, x, x2, pre, scale, bias, y, \
-                       (long)outer, (int)n, (int)scale_size, (int)bias_size, eps)
-#define ROWS_R(B, C)                                                                                            \
-    do {                                                                                                        \
-        if constexpr (!ADD) {                                                                                   \
-            if (rpw == 2) ROWS_GO(B, C, 2); else ROWS_GO(B, C, 1);                                               \
-        } else {                                                                                                \
-            ROWS_GO(B, C, 1);                                                                                   \
-        }                                                                                                       \
-    } while (0)
-    if (use8) {
-        if (c8 == 1) ROWS_R(8, 1); else ROWS_R(8, 3);
-    } else {
-        switch (c16) {
-        case 1: ROWS_R(16, 1); break;
-        case 2: ROWS_R(16, 2); break;
-        case 3: ROWS_R(16, 3); break;
-        default: ROWS_R(16, 4); break;
-        }
-    }
-#undef ROWS_R
-#undef ROWS_GO
+// What a launch needs beyond the plan; a pointer the op does not have is null.
+struct RowopArgs {
+    const void *x, *x2, *pre, *scale, *bias;
+    void *y;
+    int64_t outer, n, inner, scale_size, bias_size;
+    float eps;
+    bool rms;
+};
+
+template <auto Kern, typename... Args> static bool go(infiniRocmRuntime_t rt, const RowopPlan &pl, Args... args) {
+    const int64_t cap = pl.grid == kGridResident ? pgrid_k<Kern>(rt->num_cu) : pl.cap;
+    hipLaunchKernelGGL(Kern, dim3(rowop_grid(pl, cap)), dim3(256), 0, rt->stream, args...);
     return true;
 }
+// f(std::integral_constant<int, V>) for the V among Vs that equals v; false when none does (no such kernel is built)
+template <int V> using Int = std::integral_constant<int, V>;
+template <int... Vs, typename F> static bool pick(int v, F &&f) { return ((v == Vs && f(Int<Vs>{})) || ...); }
 
-template <typename T>
-static int softmax_dispatch(infiniRocmRuntime_t rt, const T *x, T *y, int64_t outer, int64_t dimsize,
-                            int64_t inner) {
-    constexpr int VEC = Elem<T>::VEC;
-    if (inner == 1) {
-        const bool al = is_aligned16(x) && is_aligned16(y) && (dimsize % VEC == 0);
-        const int64_t per_chunk = 64 * VEC;
-        const int chunks = (int)ceil_div(dimsize, per_chunk);
-        // rows per wave: keep ~4 KiB of loads in flight per wave
-        const int64_t row_bytes = dimsize * (int64_t)sizeof(T);
-        static const int rpw8 = getenv("IROCM_SOFTMAX_RPW8") ? atoi(getenv("IROCM_SOFTMAX_RPW8")) : 0; // tuning hook
-        const int rpw = (!al || outer < 4096) ? 1 : (row_bytes <= 1024 ? (rpw8 ? 8 : 4) : (row_bytes <= 3072 ? 2 : 1));
-#define SM_GO(C, A, R)                                                                             \
-    hipLaunchKernelGGL((softmax_wave_kernel<T, C, A, R>), dim3(pgrid_k<softmax_wave_kernel<T, C, A, R>>(ceil_div(outer, 4 * R), rt->num_cu)), \
-                       dim3(256), 0, rt->stream, x, y, (long)outer, (int)dimsize)
-        if (chunks <= 1) {
-            if (!al) SM_GO(1, false, 1);
-            else if (rpw == 8) SM_GO(1, true, 8);
-            else if (rpw == 4) SM_GO(1, true, 4);
-            else if (rpw == 2) SM_GO(1, true, 2);
-            else SM_GO(1, true, 1);
-        } else if (chunks <= 2) {
-            if (!al) SM_GO(2, false, 1);
-            else if (rpw == 4) SM_GO(2, true, 4);
-            else if (rpw == 2) SM_GO(2, true, 2);
-            else SM_GO(2, true, 1);
-        } else if (chunks <= 4) {
-            if (al) SM_GO(4, true, 1); else SM_GO(4, false, 1);
-        } else if (chunks <= 8) {
-            if (al) SM_GO(8, true, 1); else SM_GO(8, false, 1);
-        }
-        else {
-            const unsigned g = (unsigned)(outer < 8192 ? outer : 8192);
-            const int bch = (int)ceil_div(dimsize, (int64_t)256 * VEC);
-            if (al && bch <= 4)
-                hipLaunchKernelGGL((softmax_blockreg_kernel<T, 4>), dim3(g), dim3(256), 0, rt->stream, x, y, (long)outer,
-                                   (int)dimsize);
-            else if (al && bch <= 8)
-                hipLaunchKernelGGL((softmax_blockreg_kernel<T, 8>), dim3(g), dim3(256), 0, rt->stream, x, y, (long)outer,
-                                   (int)dimsize);
-            else
-                hipLaunchKernelGGL((softmax_block_kernel<T>), dim3(g), dim3(256), 0, rt->stream, x, y,
-                                   (long)outer, (long)dimsize);
-        }
-#undef SM_GO
-    } else {
-        const int64_t total = outer * inner;
-        const unsigned g = (unsigned)(ceil_div(total, 256) < 16384 ? ceil_div(total, 256) : 16384);
-        hipLaunchKernelGGL((softmax_strided_kernel<T>), dim3(g), dim3(256), 0, rt->stream, x, y,
-                           (long)outer, (long)dimsize, (long)inner);
+template <typename T, bool RMS> static bool launch_norm(infiniRocmRuntime_t rt, const RowopPlan &pl, const RowopArgs &a) {
+    const T *x = (const T *)a.x, *x2 = (const T *)a.x2, *pre = (const T *)a.pre, *scale = (const T *)a.scale, *bias = (const T *)a.bias;
+    T *y = (T *)a.y;
+    const long rows = (long)a.outer;
+    const int n = (int)a.n, ss = (int)a.scale_size, bs = (int)a.bias_size;
+    switch (pl.kernel) {
+    case kRowopNormRows:
+        return pick<0, 1, 2>(pl.add, [&](auto add) {
+            const auto rows_go = [&](auto b, auto c) {
+                return go<norm_rows_kernel<T, decltype(b)::value, decltype(c)::value, RMS, 1, decltype(add)::value>>(rt, pl, x, x2, pre, scale, bias, y, rows, n, ss, bs, a.eps);
+            };
+            return pl.B == 8 ? pick<1, 3>(pl.C, [&](auto c) { return rows_go(Int<8>{}, c); })
+                             : pick<1, 2, 3, 4>(pl.C, [&](auto c) { return rows_go(Int<16>{}, c); });
+        });
+    case kRowopNormWave:
+        return pick<1, 2, 4>(pl.C, [&](auto c) {
+            return go<norm_wave_kernel<T, decltype(c)::value, false, RMS, 1>>(rt, pl, x, scale, bias, y, rows, n, ss, bs, a.eps);
+        });
+    case kRowopNormBlockreg:
+        return pick<0, 1, 2>(pl.add, [&](auto add) {
+            return pick<2, 4, 8>(pl.C, [&](auto c) {
+                return go<norm_blockreg_kernel<T, decltype(c)::value, RMS, decltype(add)::value>>(rt, pl, x, x2, pre, scale, bias, y, rows, n, ss, bs, a.eps);
+            });
+        });
+    case kRowopNormBlock:
+        return go<norm_block_kernel<T, RMS>>(rt, pl, x, scale, bias, y, rows, (long)a.n, ss, bs, a.eps);
+    default:
+        return false;
     }
-    IROCM_LAUNCH_CHECK("softmax");
+}
+
+template <typename T> static bool launch_plan(infiniRocmRuntime_t rt, const RowopPlan &pl, const RowopArgs &a) {
+    const T *x = (const T *)a.x;
+    T *y = (T *)a.y;
+    const long rows = (long)a.outer;
+    switch (pl.kernel) {
+    case kRowopSoftmaxWave:
+        if (pl.R == 1)
+            return pick<1, 2, 4, 8>(pl.C, [&](auto c) {
+                return pl.aligned ? go<softmax_wave_kernel<T, decltype(c)::value, true, 1>>(rt, pl, x, y, rows, (int)a.n)
+                                  : go<softmax_wave_kernel<T, decltype(c)::value, false, 1>>(rt, pl, x, y, rows, (int)a.n);
+            });
+        if (pl.aligned && pl.C == 1 && pl.R == 4) // the row groups: the one R > 1 each chunk count can reach
+            return go<softmax_wave_kernel<T, 1, true, 4>>(rt, pl, x, y, rows, (int)a.n);
+        if (pl.aligned && pl.C == 2 && pl.R == 2)
+            return go<softmax_wave_kernel<T, 2, true, 2>>(rt, pl, x, y, rows, (int)a.n);
+        return false;
+    case kRowopSoftmaxBlockreg:
+        return pick<4, 8>(pl.C, [&](auto c) { return go<softmax_blockreg_kernel<T, decltype(c)::value>>(rt, pl, x, y, rows, (int)a.n); });
+    case kRowopSoftmaxBlock:
+        return go<softmax_block_kernel<T>>(rt, pl, x, y, rows, (long)a.n);
+    case kRowopSoftmaxStrided:
+        return go<softmax_strided_kernel<T>>(rt, pl, x, y, rows, (long)a.n, (long)a.inner);
+    default:
+        return a.rms ? launch_norm<T, true>(rt, pl, a) : launch_norm<T, false>(rt, pl, a);
+    }
+}
+
+static int rowop_nothing(infiniRocmRuntime_t rt) { // a zero extent
+    snprintf(rt->last_rowop_route, sizeof(rt->last_rowop_route), "none");
     return INFINI_ROCM_OK;
 }
 
-template <typename T, bool RMS>
-static int norm_dispatch(infiniRocmRuntime_t rt, const T *x, const T *scale, const T *bias, T *y,
-                         int64_t outer, int64_t n, int64_t scale_size, int64_t bias_size, float eps) {
-    constexpr int VEC = Elem<T>::VEC;
-    const bool al = is_aligned16(x) && is_aligned16(y) && is_aligned16(scale) &&
-                    (bias == nullptr || is_aligned16(bias)) && (n % VEC == 0);
-    const int chunks = (int)ceil_div(n, (int64_t)64 * VEC);
-    if (launch_norm_rows<T, RMS, 0>(rt, x, (const T *)nullptr, (const T *)nullptr, scale, bias, y, outer, n, scale_size, bias_size, eps)) {
-        IROCM_LAUNCH_CHECK("norm");
+// One row-op call after its argument checks: plan, name the route, launch. `name` goes into error texts, `what` names the launch.
+// A plan of kRowopChain launches nothing and sets *chain: the caller runs the operator chain.
+static int rowop_run(infiniRocmRuntime_t rt, RowopOp op, int dtype, const RowopArgs &a, const char *name, const char *what,
+                     bool *chain = nullptr) {
+    if (dtype != INFINI_DT_F32 && dtype != INFINI_DT_F16 && dtype != INFINI_DT_BF16)
+        IROCM_FAIL(INFINI_ROCM_UNSUPPORTED, "%s: unsupported dtype %s", name, dtype_name(dtype));
+    uintptr_t lo = 0;
+    for (const void *p : {a.x, a.x2, a.pre, a.scale, a.bias, (const void *)a.y})
+        lo |= (uintptr_t)p;
+    const RowopPlan pl = rowop_plan({op, dtype, a.outer, a.n, a.inner, a.pre != nullptr, (unsigned)(lo & 15)}, rowop_hooks(), rt->num_cu);
+    rowop_route_name(pl, rt->last_rowop_route, sizeof(rt->last_rowop_route));
+    if (pl.kernel == kRowopChain) {
+        *chain = true;
         return INFINI_ROCM_OK;
     }
-#define NORM_GO(C, A, R)                                                                           \
-    hipLaunchKernelGGL((norm_wave_kernel<T, C, A, RMS, R>), dim3(pgrid_k<norm_wave_kernel<T, C, A, RMS, R>>(ceil_div(outer, 4 * R), rt->num_cu)), \
-                       dim3(256), 0, rt->stream, x, scale, bias, y, (long)outer, (int)n,           \
-                       (int)scale_size, (int)bias_size, eps)
-    if (chunks <= 1) {
-        NORM_GO(1, false, 1);
-    } else if (chunks <= 2) {
-        NORM_GO(2, false, 1);
-    } else if (chunks <= 4) {
-        NORM_GO(4, false, 1);
-    } else {
-        const unsigned g = (unsigned)(outer < 8192 ? outer : 8192);
-        const int bch = (int)ceil_div(n, (int64_t)256 * VEC); // 16-byte chunks per thread of a block-resident row
-#define NORM_BR(C)                                                                                 \
-    hipLaunchKernelGGL((norm_blockreg_kernel<T, C, RMS, 0>), dim3(g), dim3(256), 0, rt->stream, x, (const T *)nullptr,   \
-                       (const T *)nullptr, scale, bias, y, (long)outer, (int)n, (int)scale_size, (int)bias_size, eps)
-        if (al && bch <= 2) NORM_BR(2);
-        else if (al && bch <= 4) NORM_BR(4);
-        else if (al && bch <= 8) NORM_BR(8);
-        else
-            hipLaunchKernelGGL((norm_block_kernel<T, RMS>), dim3(g), dim3(256), 0, rt->stream, x, scale,
-                               bias, y, (long)outer, (long)n, (int)scale_size, (int)bias_size, eps);
-#undef NORM_BR
-    }
-#undef NORM_GO
-    IROCM_LAUNCH_CHECK("norm");
-    return INFINI_ROCM_OK;
-}
-
-// Returns INFINI_ROCM_UNSUPPORTED (without setting an error) when the shape is outside the fused kernel's reach.
-template <typename T, bool RMS>
-static int add_norm_dispatch(infiniRocmRuntime_t rt, const T *a, const T *b, const T *pre, const T *scale, const T *bias, T *y,
-                             int64_t outer, int64_t n, int64_t scale_size, int64_t bias_size, float eps) {
-    const bool ok = pre ? launch_norm_rows<T, RMS, 2>(rt, a, b, pre, scale, bias, y, outer, n, scale_size, bias_size, eps)
-                        : launch_norm_rows<T, RMS, 1>(rt, a, b, pre, scale, bias, y, outer, n, scale_size, bias_size, eps);
-    if (!ok) {
-        // rows beyond the wave-resident kernel's 4 KiB: block-resident rows (up to 256 threads x 8 chunks x 16 B = 32 KiB)
-        constexpr int VEC = Elem<T>::VEC;
-        const bool al = is_aligned16(a) && is_aligned16(b) && (!pre || is_aligned16(pre)) && is_aligned16(y) && is_aligned16(scale) &&
-                        (bias == nullptr || is_aligned16(bias)) && (n % VEC == 0);
-        const int bch = (int)ceil_div(n, (int64_t)256 * VEC);
-        if (!al || bch > 8 || outer == 0)
-            return INFINI_ROCM_UNSUPPORTED; // the caller falls back to Add + Norm
-        const unsigned g = (unsigned)(outer < 8192 ? outer : 8192);
-#define ADD_BR(C, A)                                                                                                  \
-    hipLaunchKernelGGL((norm_blockreg_kernel<T, C, RMS, A>), dim3(g), dim3(256), 0, rt->stream, a, b, pre, scale, bias, y, \
-                       (long)outer, (int)n, (int)scale_size, (int)bias_size, eps)
-#define ADD_BRC(A)                                                                                                    \
-    do {                                                                                                              \
-        if (bch <= 2) ADD_BR(2, A); else if (bch <= 4) ADD_BR(4, A); else ADD_BR(8, A);                               \
-    } while (0)
-        if (pre) ADD_BRC(2); else ADD_BRC(1);
-#undef ADD_BRC
-#undef ADD_BR
-    }
-    IROCM_LAUNCH_CHECK("add_norm");
+    const bool ok = dtype == INFINI_DT_F32   ? launch_plan<float>(rt, pl, a)
+                    : dtype == INFINI_DT_F16 ? launch_plan<__half>(rt, pl, a)
+                                             : launch_plan<__hip_bfloat16>(rt, pl, a);
+    if (!ok)
+        IROCM_FAIL(INFINI_ROCM_UNSUPPORTED, "%s: no kernel is built for the route %s", name, rt->last_rowop_route);
+    IROCM_LAUNCH_CHECK(what);
     return INFINI_ROCM_OK;
 }
 
@@ -1015,20 +946,11 @@ int infini_rocm_softmax(infiniRocmRuntime_t rt, int dtype, const void *x, void *
     IROCM_CHECK_ARG(rt, "NULL runtime");
     IROCM_CHECK_ARG(outer >= 0 && dimsize >= 0 && inner >= 0, "softmax: negative extent");
     if (outer == 0 || dimsize == 0 || inner == 0)
-        return INFINI_ROCM_OK;
+        return rowop_nothing(rt);
     IROCM_CHECK_ARG(x && y, "softmax: NULL tensor");
     IROCM_CHECK_ARG(dimsize < (1ll << 31), "softmax: dimsize too large");
-    switch (dtype) {
-    case INFINI_DT_F32:
-        return softmax_dispatch<float>(rt, (const float *)x, (float *)y, outer, dimsize, inner);
-    case INFINI_DT_F16:
-        return softmax_dispatch<__half>(rt, (const __half *)x, (__half *)y, outer, dimsize, inner);
-    case INFINI_DT_BF16:
-        return softmax_dispatch<__hip_bfloat16>(rt, (const __hip_bfloat16 *)x, (__hip_bfloat16 *)y,
-                                                outer, dimsize, inner);
-    default:
-        IROCM_FAIL(INFINI_ROCM_UNSUPPORTED, "softmax: unsupported dtype %s", dtype_name(dtype));
-    }
+    return rowop_run(rt, kRowopSoftmax, dtype, {x, nullptr, nullptr, nullptr, nullptr, y, outer, dimsize, inner, 0, 0, 0.f, false},
+                     "softmax", "softmax");
 }
 
 int infini_rocm_layer_norm(infiniRocmRuntime_t rt, int dtype, const void *x, const void *scale,
@@ -1037,7 +959,7 @@ int infini_rocm_layer_norm(infiniRocmRuntime_t rt, int dtype, const void *x, con
     IROCM_CHECK_ARG(rt, "NULL runtime");
     IROCM_CHECK_ARG(outer >= 0 && norm_size >= 0, "layer_norm: negative extent");
     if (outer == 0 || norm_size == 0)
-        return INFINI_ROCM_OK;
+        return rowop_nothing(rt);
     IROCM_CHECK_ARG(x && y && scale, "layer_norm: NULL tensor");
     IROCM_CHECK_ARG(scale_size == 1 || scale_size == norm_size,
                     "layer_norm: scale has %lld elements, expected 1 or %lld", (long long)scale_size,
@@ -1046,22 +968,8 @@ int infini_rocm_layer_norm(infiniRocmRuntime_t rt, int dtype, const void *x, con
                     "layer_norm: bias has %lld elements, expected 1 or %lld", (long long)bias_size,
                     (long long)norm_size);
     IROCM_CHECK_ARG(norm_size < (1ll << 31), "layer_norm: norm_size too large");
-    switch (dtype) {
-    case INFINI_DT_F32:
-        return norm_dispatch<float, false>(rt, (const float *)x, (const float *)scale,
-                                           (const float *)bias, (float *)y, outer, norm_size,
-                                           scale_size, bias_size, eps);
-    case INFINI_DT_F16:
-        return norm_dispatch<__half, false>(rt, (const __half *)x, (const __half *)scale,
-                                            (const __half *)bias, (__half *)y, outer, norm_size,
-                                            scale_size, bias_size, eps);
-    case INFINI_DT_BF16:
-        return norm_dispatch<__hip_bfloat16, false>(
-            rt, (const __hip_bfloat16 *)x, (const __hip_bfloat16 *)scale, (const __hip_bfloat16 *)bias,
-            (__hip_bfloat16 *)y, outer, norm_size, scale_size, bias_size, eps);
-    default:
-        IROCM_FAIL(INFINI_ROCM_UNSUPPORTED, "layer_norm: unsupported dtype %s", dtype_name(dtype));
-    }
+    return rowop_run(rt, kRowopLayerNorm, dtype, {x, nullptr, nullptr, scale, bias, y, outer, norm_size, 1, scale_size, bias_size, eps, false},
+                     "layer_norm", "norm");
 }
 
 int infini_rocm_add_norm(infiniRocmRuntime_t rt, int dtype, int rms, const void *a, const void *b, const void *scale,
@@ -1076,24 +984,14 @@ int infini_rocm_bias_add_norm(infiniRocmRuntime_t rt, int dtype, int rms, const 
     IROCM_CHECK_ARG(rt, "NULL runtime");
     IROCM_CHECK_ARG(outer >= 0 && norm_size >= 0 && norm_size < (1ll << 31), "add_norm: bad extent");
     if (outer == 0 || norm_size == 0)
-        return INFINI_ROCM_OK;
+        return rowop_nothing(rt);
     IROCM_CHECK_ARG(a && b && y && scale, "add_norm: NULL tensor");
     IROCM_CHECK_ARG(scale_size == 1 || scale_size == norm_size, "add_norm: bad scale size");
     IROCM_CHECK_ARG(bias == nullptr || bias_size == 1 || bias_size == norm_size, "add_norm: bad bias size");
-    int st = INFINI_ROCM_UNSUPPORTED;
-#define GO(T)                                                                                                   \
-    st = rms ? add_norm_dispatch<T, true>(rt, (const T *)a, (const T *)b, (const T *)pre, (const T *)scale, (const T *)bias, \
-                                          (T *)y, outer, norm_size, scale_size, bias_size, eps)                \
-             : add_norm_dispatch<T, false>(rt, (const T *)a, (const T *)b, (const T *)pre, (const T *)scale, (const T *)bias, \
-                                           (T *)y, outer, norm_size, scale_size, bias_size, eps)
-    switch (dtype) {
-    case INFINI_DT_F32: GO(float); break;
-    case INFINI_DT_F16: GO(__half); break;
-    case INFINI_DT_BF16: GO(__hip_bfloat16); break;
-    default: IROCM_FAIL(INFINI_ROCM_UNSUPPORTED, "add_norm: unsupported dtype %s", dtype_name(dtype));
-    }
-#undef GO
-    if (st != INFINI_ROCM_UNSUPPORTED)
+    bool chain = false;
+    int st = rowop_run(rt, kRowopAddNorm, dtype, {a, b, pre, scale, bias, y, outer, norm_size, 1, scale_size, bias_size, eps, rms != 0},
+                       "add_norm", "add_norm", &chain);
+    if (!chain)
         return st;
     // outside the fused kernel's reach (long or unaligned rows): the operator chain, in place over y. y may BE a or b (the
     // planner allows the row-wise in-place forms): with a row bias the two Adds run as ONE element-wise pass
@@ -1107,8 +1005,10 @@ int infini_rocm_bias_add_norm(infiniRocmRuntime_t rt, int dtype, int rms, const 
     }
     if (st != INFINI_ROCM_OK)
         return st;
-    return rms ? infini_rocm_rms_norm(rt, dtype, y, scale, y, outer, norm_size, eps)
-               : infini_rocm_layer_norm(rt, dtype, y, scale, bias, y, outer, norm_size, scale_size, bias_size, eps);
+    st = rms ? infini_rocm_rms_norm(rt, dtype, y, scale, y, outer, norm_size, eps)
+             : infini_rocm_layer_norm(rt, dtype, y, scale, bias, y, outer, norm_size, scale_size, bias_size, eps);
+    snprintf(rt->last_rowop_route, sizeof(rt->last_rowop_route), "chain"); // (the norm's own route until here)
+    return st;
 }
 
 int infini_rocm_rms_norm(infiniRocmRuntime_t rt, int dtype, const void *x, const void *w, void *y,
@@ -1116,24 +1016,32 @@ int infini_rocm_rms_norm(infiniRocmRuntime_t rt, int dtype, const void *x, const
     IROCM_CHECK_ARG(rt, "NULL runtime");
     IROCM_CHECK_ARG(outer >= 0 && norm_size >= 0, "rms_norm: negative extent");
     if (outer == 0 || norm_size == 0)
-        return INFINI_ROCM_OK;
+        return rowop_nothing(rt);
     IROCM_CHECK_ARG(x && y && w, "rms_norm: NULL tensor");
     IROCM_CHECK_ARG(norm_size < (1ll << 31), "rms_norm: norm_size too large");
-    switch (dtype) {
-    case INFINI_DT_F32:
-        return norm_dispatch<float, true>(rt, (const float *)x, (const float *)w, nullptr, (float *)y,
-                                          outer, norm_size, norm_size, 0, eps);
-    case INFINI_DT_F16:
-        return norm_dispatch<__half, true>(rt, (const __half *)x, (const __half *)w, nullptr,
-                                           (__half *)y, outer, norm_size, norm_size, 0, eps);
-    case INFINI_DT_BF16:
-        return norm_dispatch<__hip_bfloat16, true>(rt, (const __hip_bfloat16 *)x,
-                                                   (const __hip_bfloat16 *)w, nullptr,
-                                                   (__hip_bfloat16 *)y, outer, norm_size, norm_size, 0,
-                                                   eps);
-    default:
-        IROCM_FAIL(INFINI_ROCM_UNSUPPORTED, "rms_norm: unsupported dtype %s", dtype_name(dtype));
-    }
+    return rowop_run(rt, kRowopRmsNorm, dtype, {x, nullptr, nullptr, w, nullptr, y, outer, norm_size, 1, norm_size, 0, eps, true},
+                     "rms_norm", "norm");
+}
+
+int infini_rocm_rowop_last_route(infiniRocmRuntime_t rt, const char **route) {
+    IROCM_CHECK_ARG(rt && route, "NULL argument");
+    *route = rt->last_rowop_route;
+    return INFINI_ROCM_OK;
+}
+
+// rowop_plan without a runtime or a GPU; ptr_lo stands for the pointers of the launch entries.
+int infini_rocm_rowop_plan_route(int op, int dtype, int64_t outer, int64_t n, int64_t inner, int has_pre, int ptr_lo, int num_cu,
+                                 char *route, size_t cap) {
+    IROCM_CHECK_ARG(route && cap > 0, "NULL argument");
+    IROCM_CHECK_ARG(op >= 0 && op < kNumRowopOps && num_cu > 0, "rowop: bad op %d / CU count %d", op, num_cu);
+    IROCM_CHECK_ARG(dtype == INFINI_DT_F32 || dtype == INFINI_DT_F16 || dtype == INFINI_DT_BF16, "rowop: unsupported dtype %s",
+                    dtype_name(dtype));
+    IROCM_CHECK_ARG(outer >= 0 && n >= 0 && inner >= 0 && n < (1ll << 31), "rowop: bad extent");
+    IROCM_CHECK_ARG(op == kRowopSoftmax || inner == 1, "rowop: only softmax has an inner extent");
+    rowop_route_name(rowop_plan({(RowopOp)op, dtype, outer, n, inner, op == kRowopAddNorm && has_pre, (unsigned)ptr_lo & 15}, rowop_hooks(),
+                                num_cu),
+                     route, cap);
+    return INFINI_ROCM_OK;
 }
 
 } // extern "C"

@@ -326,6 +326,42 @@ def rms_norm(rt: RocmRuntime, x: torch.Tensor, weight: torch.Tensor, eps: float 
     return out
 
 
+ROWOPS = ("softmax", "layer_norm", "rms_norm", "add_norm")  # infini_rocm_rowop_plan_route's `op`, in order
+# the tensors each entry is given (bias may be None, pre only with has_pre): their addresses decide the alignment
+_ROWOP_TENSORS = {"softmax": ("x", "y"), "layer_norm": ("x", "y", "scale", "bias"), "rms_norm": ("x", "y", "scale"),
+                  "add_norm": ("a", "b", "pre", "y", "scale", "bias")}
+
+
+def rowop_ptr_lo(op: str, has_pre: bool = False, **address: int) -> int:
+    """infini_rocm_rowop_plan_route's ptr_lo from addresses by tensor name: the OR of the low four bits of those the op is given; a
+    name the op has no tensor for (a scale of softmax, a pre without has_pre) does not count."""
+    lo = 0
+    for name in _ROWOP_TENSORS[op]:
+        if name != "pre" or has_pre:
+            lo |= int(address.get(name, 0)) & 15
+    return lo
+
+
+def rowop_last_route(rt: RocmRuntime) -> str:
+    """The kernel and template choices the most recent softmax / layer_norm / rms_norm / add_norm / bias_add_norm call on this runtime
+    launched, e.g. "norm_rows/B8/C3/ADD1"; "chain" for an add_norm that ran Add and the norm separately (include/infini_rocm.h)."""
+    v = C.c_char_p()
+    check(lib().infini_rocm_rowop_last_route(rt.handle, C.byref(v)))
+    return v.value.decode()
+
+
+def rowop_plan_route(op: str, dtype: torch.dtype, outer: int, n: int, inner: int = 1, has_pre: bool = False, ptr_lo: int = 0,
+                     num_cu: int = 256) -> str:
+    """The route that call would take (infini_rocm_rowop_plan_route: pure, no GPU). op: one of ROWOPS (has_pre: bias_add_norm's row);
+    ptr_lo: the OR of the low four address bits of its tensors (data_ptr() & 15)."""
+    if op not in ROWOPS:
+        raise ValueError(f"rowop_plan_route: op must be one of {ROWOPS}")
+    buf = C.create_string_buffer(64)
+    check(lib().infini_rocm_rowop_plan_route(ROWOPS.index(op), int(_TORCH2DT[dtype]), outer, n, inner, int(has_pre), int(ptr_lo), int(num_cu),
+                                             buf, len(buf)))
+    return buf.value.decode()
+
+
 def attention(rt: RocmRuntime, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float | torch.Tensor,
               mask: torch.Tensor | None = None, causal: bool = False, scale_is_div: bool = False,
               out: torch.Tensor | None = None, head_merge: int = 0) -> torch.Tensor:

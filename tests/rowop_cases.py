@@ -4,17 +4,16 @@ Softmax, LayerNorm, RMSNorm and the fused add_norm / bias_add_norm. numpy and or
 route(op, dt, outer, n, inner, aligned, add, has_pre) restates softmax_dispatch, norm_dispatch, launch_norm_rows and
 add_norm_dispatch: VEC = 4 (f32) / 8 (16-bit), chunks of 64 VEC elements, the 4096-byte limit of norm_rows_kernel with its chunk-width
 rule (8-byte chunks where c8 = ceil(bytes / 512) is 1 or 3 and leaves fewer idle lanes), 256 VEC {2, 4, 8} for the block-resident
-kernels and the row groups (R = 4 up to 1024 bytes, R = 2 up to 3072, from 4096 aligned rows on). rowops.hip reports no route, so a
-case DECLARES the route it was built for (from the ranges written in _softmax_ranges and _norm_ranges) and
-tests/test_rowop_selectors_cpu.py holds the mirror against the declarations and the table against everything the mirror can return.
+kernels and the row groups (R = 4 up to 1024 bytes, R = 2 up to 3072, from 4096 aligned rows on). A case DECLARES the route it was
+built for (from the ranges written in _softmax_ranges and _norm_ranges); tests/test_rowop_selectors_cpu.py holds the mirror against the
+declarations and the table against everything the mirror can return, tests/test_rowop_route_cpu.py holds the mirror against the planner
+of csrc/rowops_route.h (ops.rowop_plan_route), and the GPU file asserts after every launch that ops.rowop_last_route names the declared route.
 
-Instantiations no shape reaches (read from the dispatch), and what is left out:
-  softmax_wave_kernel<T, 2, true, 4>   two chunks are more than 1024 bytes, and R = 4 is chosen up to 1024 bytes only
-  softmax_wave_kernel<T, 1, true, 2>   one chunk is at most 1024 bytes, which always takes R = 4 (R = 2 starts above 1024)
-  norm_wave_kernel<.., ALIGNED = true> aligned rows up to 4096 bytes all go to norm_rows_kernel; no NORM_GO names it
+Template values the kernels accept that no route names, so they are not built:
+  norm_wave_kernel<.., ALIGNED = true> aligned rows up to 4096 bytes all go to norm_rows_kernel
   norm_wave_kernel<.., ROWS = 2>       likewise never named
-  softmax_wave_kernel<T, 1, true, 8>   only with IROCM_SOFTMAX_RPW8, read once per process into a static: not switchable in a test
-  norm_rows_kernel<.., ROWS = 2, 0>    only with IROCM_NORM_RPW = 2, a static as well
+(softmax_wave_kernel's ROWS = 8 and norm_rows_kernel's ROWS = 2 lost their launch sites with the hooks that chose them:
+docs/history/rowops_dropped_hooks.md.)
 
 Inputs. Every launch is made of PATTERN rows: a family holds P rows [P, n] with their expectation and bound, and row r of a launch
 is pattern (base + r) mod P (consecutive rows always differ). A case with few rows walks the patterns in rounds (base = round *

@@ -3,7 +3,7 @@ per-element bound of tests/rowop_cases.py (proved on the oracle alone in tests/t
 of the dispatch can return, in f32, f16 and bf16, one test per (operator, dtype, route) with the cases of that route inside — its
 smallest and largest n and one with a partial last chunk, 1 row and 5, the ALIGNED = false kernels through an odd n and through
 views one element off a 16-byte boundary, the row groups R = 2 and R = 4 at 4096 + 3 rows and a second trip of every persistent or
-grid-stride loop.
+grid-stride loop. After every launch ops.rowop_last_route must name the route the case declares ("chain" for the add-norm chain).
 
 Every launch: the operands and the output (given through out=) are views into blocks with SLACK elements on both sides, the
 operand blocks filled with 1000, the output block with 7. Asserted in this order: the whole output is within the bound of its row
@@ -125,10 +125,13 @@ def run_family(rt, cs, fam):
 
         def launch(a_, b_, out_):
             if cs.op == "softmax":
-                return ops.softmax(rt, a_, 1, out=out_)
-            if cs.op == "add_norm":
-                return ops.add_layer_norm(rt, a_, b_, g, b, cs.eps, cs.rms, out=out_, pre=pre)
-            return ops.rms_norm(rt, a_, g, cs.eps, out=out_) if cs.rms else ops.layer_norm(rt, a_, g, b, cs.eps, -1, out=out_)
+                got = ops.softmax(rt, a_, 1, out=out_)
+            elif cs.op == "add_norm":
+                got = ops.add_layer_norm(rt, a_, b_, g, b, cs.eps, cs.rms, out=out_, pre=pre)
+            else:
+                got = ops.rms_norm(rt, a_, g, cs.eps, out=out_) if cs.rms else ops.layer_norm(rt, a_, g, b, cs.eps, -1, out=out_)
+            assert ops.rowop_last_route(rt) == cs.route, f"{what}: launched {ops.rowop_last_route(rt)}, the case is built for {cs.route}"
+            return got
 
         def rows_of(t):
             return t if cs.inner == 1 else t.permute(0, 2, 1).reshape(cs.outer * cs.inner, n)
