@@ -12,8 +12,12 @@
 //   * per k-step and wave: 64 MFMAs (8 x 8 tiles of v_mfma_f32_16x16x32), the fragment reads of the NEXT k-step (stage s + 1 into the
 //     other register set), 8 LDS-DMA pieces of the k-step THREE ahead (stage s + 3: the stage whose reads ended at the last barrier),
 //     s_waitcnt vmcnt(8) — the pieces issued one step ago — and one barrier;
-//   * inside a group of eight MFMAs (accumulator row i): A reads behind MFMA 0 / 1, B reads behind MFMA 2 / 3, s_add m0 behind MFMA 4,
-//     the piece behind MFMA 6 — inline asm throughout, accumulators pinned to AGPRs ("+a"), fragments to VGPRs;
+//   * inside a group of eight MFMAs (accumulator row i) every gap between two MFMAs holds at most ONE other instruction, assigned by
+//     the gap map below (gap_busy / adv_map): a fragment read behind MFMA 0 .. 3 (packed into the earliest rows where a K-major
+//     operand leaves read gaps over), s_add m0 / the piece behind MFMA 4 / 5 and 6 / 7, and the k advance of a lane offset as one
+//     v_add_u32 in an otherwise empty gap behind the offset's last piece of the step — inline asm throughout, accumulators pinned to
+//     AGPRs ("+a"), fragments to VGPRs; between a step's first MFMA and its barrier the compiler places nothing but its s_nop 0
+//     in front of an s_add m0 and the K loop's counter (read the disassembly of all eight builds after a change to the loop);
 //   * persistent over tiles (XCD-chunked, 4-row groups), the k-step stream runs THROUGH tile boundaries: the last three steps of a tile
 //     request the next tile's first three, the epilogue (permlane16 swap -> 16-byte stores) runs under them;
 //   * a workgroup's LAST tile ends differently (final_block below): its last three k-steps request nothing and run ROW-major, so
@@ -147,6 +151,114 @@ constexpr int slot_piece(int n, int I, int slot) {
     return slot == 0 ? I : (8 + I < n ? 8 + I : -1);
 }
 
+// The GAP MAP of a k-step. Gap g = 8 I + J is the issue slot behind MFMA J of accumulator row I; a gap holds at most ONE instruction.
+//   * fragment reads of the next k-step: gaps J = 0 .. 3, one read per gap in the EARLIEST rows, in the order of use (per fragment f:
+//     A's read(s), then B's): 32 reads with two M/N-major operands (fragment I in row I), 24 with one (rows 0 .. 5), 16 with none
+//     (rows 0 .. 3) — the boundary's lgkmcnt(0) then waits for reads issued at least 32 MFMAs earlier;
+//   * pieces: s_add m0 / the LDS-DMA load in gaps J = 4 / 5 (slot 0) and 6 / 7 (slot 1) of the rows slot_piece names;
+//   * the k advance of a lane offset (four per operand; due in every step that requests from it): ONE v_add_u32 in the first gap
+//     behind the step's last piece that reads the offset which holds nothing else. Where a step leaves no such gap (both operands
+//     K-major, odd steps: sixteen pieces, the last in row 7, J = 7) the add goes into the first empty gap of the FOLLOWING step, ahead
+//     of that step's first piece off the same offset (there: none, a K-major operand requests nothing on even steps).
+// Left to the compiler, the advances become induction variables and land as clumps of three to eight VALU adds in front of the barriers
+// and behind them — on the one stretch of a step where no MFMA covers them.
+struct ReadSel {
+    int oper, f, half;
+};
+template <bool AKM, bool BKM> constexpr int step_reads() { return 32 - (AKM ? 8 : 0) - (BKM ? 8 : 0); }
+template <bool AKM, bool BKM> constexpr ReadSel read_sel(int r) {
+    const int na = AKM ? 1 : 2, per = na + (BKM ? 1 : 2), f = r / per, w = r % per;
+    return w < na ? ReadSel{0, f, w} : ReadSel{1, f, w - na};
+}
+template <bool AKM, bool BKM> constexpr bool gap_busy(int S, int g) {
+    const int I = g >> 3, J = g & 7;
+    return J < 4 ? I * 4 + J < step_reads<AKM, BKM>() : slot_piece(step_pieces<AKM, BKM>(S), I, (J - 4) >> 1) >= 0;
+}
+// gap of the first (last = false) / last load in step S that reads lane offset k = 4 oper + idx; -1: the step requests nothing off it
+template <bool AKM, bool BKM> constexpr int offset_use(int S, int k, bool last) {
+    const int np = step_pieces<AKM, BKM>(S);
+    int found = -1;
+    for (int g = 0; g < 64; ++g) {
+        const int I = g >> 3, J = g & 7;
+        if (J != 5 && J != 7)
+            continue;
+        const int q = slot_piece(np, I, (J - 4) >> 1);
+        if (q < 0)
+            continue;
+        const PieceSel ps = piece_sel<AKM, BKM>(S, q);
+        if (ps.oper * 4 + ps.idx != k)
+            continue;
+        if (!last)
+            return g;
+        found = g;
+    }
+    return found;
+}
+struct AdvMap {
+    int own[8]; // gap of the add due in this step; -1: none due, or no gap left behind the last use (then it is in `in` of the next step)
+    int in[8];  // gap of the add the previous step could not place; -1: none
+};
+template <bool AKM, bool BKM> constexpr AdvMap adv_own(int S) {
+    AdvMap m{};
+    bool taken[64] = {};
+    for (int g = 0; g < 64; ++g) taken[g] = gap_busy<AKM, BKM>(S, g);
+    for (int k = 0; k < 8; ++k) {
+        m.own[k] = m.in[k] = -1;
+        const int lu = offset_use<AKM, BKM>(S, k, true);
+        if (lu < 0)
+            continue;
+        for (int g = lu + 1; g < 64; ++g)
+            if (!taken[g]) {
+                taken[g] = true;
+                m.own[k] = g;
+                break;
+            }
+    }
+    return m;
+}
+template <bool AKM, bool BKM> constexpr bool adv_deferred(int S, int k) {
+    return offset_use<AKM, BKM>(S, k, true) >= 0 && adv_own<AKM, BKM>(S).own[k] < 0;
+}
+template <bool AKM, bool BKM> constexpr AdvMap adv_map(int S) {
+    AdvMap m = adv_own<AKM, BKM>(S);
+    bool taken[64] = {};
+    for (int g = 0; g < 64; ++g) taken[g] = gap_busy<AKM, BKM>(S, g);
+    for (int k = 0; k < 8; ++k)
+        if (m.own[k] >= 0)
+            taken[m.own[k]] = true;
+    for (int k = 0; k < 8; ++k) {
+        if (!adv_deferred<AKM, BKM>((S + 3) & 3, k))
+            continue;
+        for (int g = 0; g < 64; ++g)
+            if (!taken[g]) {
+                taken[g] = true;
+                m.in[k] = g;
+                break;
+            }
+    }
+    return m;
+}
+// lane offset advanced in gap g of step S; -1: none
+template <bool AKM, bool BKM> constexpr int adv_at(int S, int g) {
+    const AdvMap m = adv_map<AKM, BKM>(S);
+    for (int k = 0; k < 8; ++k)
+        if (m.own[k] == g || m.in[k] == g)
+            return k;
+    return -1;
+}
+// every add has its gap, and an add that moved into the following step stands ahead of that step's first piece off its offset
+template <bool AKM, bool BKM> constexpr bool adv_map_ok() {
+    for (int S = 0; S < 4; ++S) {
+        const AdvMap m = adv_map<AKM, BKM>(S);
+        for (int k = 0; k < 8; ++k) {
+            const int fu = offset_use<AKM, BKM>(S, k, false);
+            if (adv_deferred<AKM, BKM>((S + 3) & 3, k) && (m.in[k] < 0 || (fu >= 0 && m.in[k] > fu)))
+                return false;
+        }
+    }
+    return true;
+}
+
 // The final block's epilogue of one accumulator row as 60 single instructions, in the order they are issued one to three per MFMA gap
 // of the NEXT row: P(jp) = the 8 accumulator reads and 4 packed converts of column-tile pair jp (read, read, convert; 12), W(jp) = its
 // two lane-group swaps, T(jp) = its 16-byte store. Order P0 P1 W0 P2 T0 W1 P3 T1 W2 T2 W3 T3: at least four instructions lie between a
@@ -258,7 +370,20 @@ __global__ __launch_bounds__(256, 1) void gemm128w_kernel(WArgs pw) {
         constexpr int OP = decltype(operc)::value, IDX = decltype(idxc)::value, IMM = decltype(immc)::value;
         const unsigned off = OP == 0 ? a_off[IDX] : b_off[IDX]; // (copies: clang does not capture a variable a generic lambda names
         const char *base = OP == 0 ? pa : pb;                   //  only in an asm operand)
+        // (default cache policy for both kinds of piece: `nt` on the M/N-major ones cost 13 %, `sc0` nothing either way —
+        // profiles/gemm128w_kstep_ab.txt)
         asm volatile("global_load_lds_dwordx4 %0, %1 offset:%2" ::"v"(off), "s"(base), "i"(IMM) : "memory");
+    };
+    // the k advance of one lane offset as ONE instruction that stays where it is written (the gap map above)
+    auto bump = [&](auto operc, auto idxc) __attribute__((always_inline)) {
+        constexpr int OP = decltype(operc)::value, IDX = decltype(idxc)::value;
+        unsigned &off = OP == 0 ? a_off[IDX] : b_off[IDX];
+        if constexpr (OP == 0 ? AKM : BKM) {
+            asm volatile("v_add_u32 %0, 0x80, %0" : "+v"(off));
+        } else {
+            const unsigned by = OP == 0 ? a_kstep : b_kstep;
+            asm volatile("v_add_u32 %0, %1, %0" : "+v"(off) : "s"(by));
+        }
     };
     // (the instruction offset of an LDS-DMA load moves BOTH addresses, memory and LDS: IMM is taken back out of M0)
     auto set_m0 = [&m0w](auto stc, auto operc, auto idxc, auto immc) __attribute__((always_inline)) {
@@ -293,6 +418,18 @@ __global__ __launch_bounds__(256, 1) void gemm128w_kernel(WArgs pw) {
             else b_off[i] += by;
         }
     };
+    // the prologue's last advance stands for step 3's: an offset whose add step 3 hands on to step 0 (gap map) is left to step 0 here too
+    auto advance_entry = [&](auto operc, unsigned by) __attribute__((always_inline)) {
+        constexpr int OP = decltype(operc)::value;
+        sfor<4>([&](auto idxc) {
+            constexpr int IDX = decltype(idxc)::value;
+            if constexpr (!adv_deferred<AKM, BKM>(3, OP * 4 + IDX)) {
+                if constexpr (OP == 0) a_off[IDX] += by;
+                else b_off[IDX] += by;
+            }
+        });
+    };
+    static_assert(adv_map_ok<AKM, BKM>(), "gap map: an offset's add has no gap");
     constexpr std::integral_constant<int, 0> kA{};
     constexpr std::integral_constant<int, 1> kB{};
 
@@ -324,10 +461,10 @@ __global__ __launch_bounds__(256, 1) void gemm128w_kernel(WArgs pw) {
     if constexpr (BKM) request(std::integral_constant<int, 2>{}, kB);
     if constexpr (!AKM) request(std::integral_constant<int, 2>{}, kA);
     if constexpr (!BKM) request(std::integral_constant<int, 2>{}, kB);
-    if constexpr (AKM) advance(kA, 128);
-    else advance(kA, a_kstep);
-    if constexpr (BKM) advance(kB, 128);
-    else advance(kB, b_kstep);
+    if constexpr (AKM) advance_entry(kA, 128);
+    else advance_entry(kA, a_kstep);
+    if constexpr (BKM) advance_entry(kB, 128);
+    else advance_entry(kB, b_kstep);
     constexpr int kG1 = 4 * nMN, kG2 = 8 * nKM + 4 * nMN;
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kG1 + kG2) : "memory");
     __builtin_amdgcn_s_barrier();
@@ -352,10 +489,15 @@ __global__ __launch_bounds__(256, 1) void gemm128w_kernel(WArgs pw) {
             sfor<8>([&](auto jc) {
                 constexpr int J = decltype(jc)::value;
                 mfma_a<Tr, FIRST>(acc[I][J], fb.template get<CUR, J>(), fa.template get<CUR, I>());
-                if constexpr (J == 0) fa.template read0<NXT, I, RS>();
-                if constexpr (J == 1) fa.template read1<NXT, I, RS>();
-                if constexpr (J == 2) fb.template read0<NXT, I, RS>();
-                if constexpr (J == 3) fb.template read1<NXT, I, RS>();
+                if constexpr (J < 4 && I * 4 + J < step_reads<AKM, BKM>()) {
+                    constexpr ReadSel rs = read_sel<AKM, BKM>(I * 4 + J);
+                    if constexpr (rs.oper == 0 && rs.half == 0) fa.template read0<NXT, rs.f, RS>();
+                    if constexpr (rs.oper == 0 && rs.half == 1) fa.template read1<NXT, rs.f, RS>();
+                    if constexpr (rs.oper == 1 && rs.half == 0) fb.template read0<NXT, rs.f, RS>();
+                    if constexpr (rs.oper == 1 && rs.half == 1) fb.template read1<NXT, rs.f, RS>();
+                }
+                constexpr int ADV = adv_at<AKM, BKM>(S, I * 8 + J);
+                if constexpr (ADV >= 0) bump(std::integral_constant<int, (ADV >> 2)>{}, std::integral_constant<int, (ADV & 3)>{});
                 if constexpr (J >= 4) {
                     constexpr int Q = slot_piece(NP, I, (J - 4) >> 1);
                     if constexpr (Q >= 0) {
@@ -369,19 +511,15 @@ __global__ __launch_bounds__(256, 1) void gemm128w_kernel(WArgs pw) {
                 }
             });
         });
-        // the pieces of the steps after this one: the next k-step (pair) of this tile, or — behind the tile's fourth-last step, where both
-        // kinds of operand have requested everything of this tile — the next tile's first
+        // The offsets moved on to the next k-step (pair) of this tile in their gaps. Behind the tile's fourth-last step, where both kinds
+        // of operand have requested everything of this tile, they go back by the tile's whole k advance and the corner becomes the next
+        // tile's (once per tile: these eight adds may stand together)
         if (S == 0 && last_block) {
             pa = na;
             pb = nb;
             pin();
-            advance(kA, AKM ? 0u - a_span : a_kstep - a_span);
-            advance(kB, BKM ? 0u - b_span : b_kstep - b_span);
-        } else {
-            if constexpr (!AKM) advance(kA, a_kstep);
-            else if constexpr (S & 1) advance(kA, 128);
-            if constexpr (!BKM) advance(kB, b_kstep);
-            else if constexpr (S & 1) advance(kB, 128);
+            advance(kA, 0u - a_span);
+            advance(kB, 0u - b_span);
         }
         asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NP) : "memory");
         __builtin_amdgcn_s_barrier();
